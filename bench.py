@@ -12,10 +12,14 @@ resident in HBM, float64) over one synthetic assembly.
              region.  The matrix (320 GB in float64) does not fit one GPU, which is why N=1 runs config 2; the
              work is the same for N = 2, 4, 8 ("strong" scaling), and pairs/s is comparable across all N.
 
-Beside `value` the JSON line carries: the roofline of the dominant kernel (HIP-event time on the launch stream),
+A plain run sets up, warms up, times --steps steps and prints the JSON line: `value`, `ms_per_step`, the workload and,
+for N>1, the time of the single exchange (all-gather).  --dump-outputs DIR also writes what the last timed step computed
+(a fixed, seeded sample of the float64 matrix, at most 64 MB) as DIR/*.npy.
+
+With --full the JSON line also carries: the roofline of the dominant kernel (HIP-event time on the launch stream),
 the same for the other single-GPU BASELINE configs (C3 Eucl on both its paths, C5 BC) and for the general JSD
 kernel that ragged assemblies get, the CPU baseline (oracle = the reference's joblib path restated) and, for N>1,
-the times of the single exchange (all-gather) and of the optional row-completing exchange.
+the per-rank kernel times and the time of the optional row-completing exchange.  The --no-* switches trim --full.
 """
 import argparse
 import json
@@ -154,6 +158,51 @@ def hbm_roofline(algo_bytes, ms, **extra):
     return d
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: the .npy files stay under 64 MB in all, headers included
+
+
+def output_views(plan, rank, slab, mirrors):
+    """(name, 2-D tensor) for everything one step writes on this rank: the whole matrix for one rank, else every block and
+    mirror block of the rank's work list"""
+    if plan.world == 1:
+        return [("distances", slab)]
+    views = []
+    for k, b in enumerate(plan.blocks(rank, slab, mirrors)):
+        views.append(("distances_rank%d_block%d" % (rank, k), b["out"]))
+        if b.get("mirror") is not None:
+            views.append(("distances_rank%d_block%d_mirror" % (rank, k), b["mirror"]))
+    return views
+
+
+def sample_matrix(view, budget, rng):
+    """(suffix, numpy array) of a 2-D tensor within `budget` bytes: the whole of it when it fits, else seeded whole rows
+    (half the budget) and seeded single entries (the other half)"""
+    import torch
+    rows, cols = view.shape
+    item = view.element_size()
+    if rows * cols * item <= budget:
+        return [("all", view.cpu().numpy())]
+    out = []
+    nr = min(rows, budget // 2 // (cols * item))
+    if nr > 0:
+        r = torch.from_numpy(np.sort(rng.choice(rows, nr, replace=False))).to(view.device)
+        out.append(("rows", view[r].cpu().numpy()))
+    flat = rng.integers(0, rows * cols, budget // 2 // item, dtype=np.int64)
+    i, j = torch.from_numpy(flat // cols).to(view.device), torch.from_numpy(flat % cols).to(view.device)
+    out.append(("entries", view[i, j].cpu().numpy()))
+    return out
+
+
+def dump_outputs(out_dir, plan, rank, slab, mirrors):
+    """DIR/<name>.npy of what the last step left in this rank's slab and mirror blocks; the same arguments give the same
+    samples, so two builds can be compared file by file"""
+    nviews = sum(1 + (kind != "diag") for r in range(plan.world) for _, _, kind, _ in plan.work(r))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (name, view) in enumerate(output_views(plan, rank, slab, mirrors)):
+        for suffix, arr in sample_matrix(view, DUMP_BUDGET_BYTES // nviews, np.random.default_rng([rank, k])):
+            np.save(os.path.join(out_dir, "%s_%s.npy" % (name, suffix)), arr)
+
+
 def path_lines(ctx, seq, offsets, counts, totals, n, dim, metric, pattern, dev, stage1_ms, matrix_ms):
     """Every step of the path either side of the timed matrix, each as its own line (reference: main(),
     /root/reference/phylopackage/bin/phyloligo.py:1036-1068 - read the assembly, profile, distances, write).
@@ -279,17 +328,25 @@ def main():
     ap.add_argument("--length", type=int, default=2000)
     ap.add_argument("--metric", default="JSD", choices=["Eucl", "JSD", "KT", "BC", "SC"])
     ap.add_argument("--pattern", default="1111")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C3 / C5 / KT extras in config.other_configs")
-    ap.add_argument("--no-ragged", action="store_true", help="skip config.ragged_assembly (a real-assembly-like input of the same "
-                                                             "number of contigs through every metric)")
-    ap.add_argument("--no-complete-rows", action="store_true", help="N>1: skip timing the optional row-completing exchange")
-    ap.add_argument("--no-path-lines", action="store_true", help="skip config.path_lines (H2D, D2H, container write, end-to-end CLI wall)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed to DIR/*.npy "
+                                                          "(float64; a fixed, seeded sample when the matrix is above 60 MB)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: stage 1, kernel times and "
+                                                        "rooflines, the general JSD kernel, other configs, the ragged assembly, "
+                                                        "path lines, the CPU baseline and (N>1) the row-completing exchange")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the C3 / C5 / KT extras in config.other_configs")
+    ap.add_argument("--no-ragged", action="store_true", help="--full: skip config.ragged_assembly (a real-assembly-like input of the "
+                                                             "same number of contigs through every metric)")
+    ap.add_argument("--no-complete-rows", action="store_true", help="--full, N>1: skip timing the optional row-completing exchange")
+    ap.add_argument("--no-path-lines", action="store_true", help="--full: skip config.path_lines (H2D, D2H, container write, "
+                                                                 "end-to-end CLI wall)")
     ap.add_argument("--complete-rows-timeout", type=float, default=300.0,
                     help="seconds the optional row-completing exchange of an N > 1 run may take before the record is printed without it")
     ap.add_argument("--launch-timeout", type=float, default=float(os.environ.get("PO_BENCH_LAUNCH_TIMEOUT", "3000")),
                     help="--gpus N>1 started plainly: seconds after which the launcher kills its ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` with N > 1 and no WORLD_SIZE: this process becomes the launcher (it has imported neither torch
     # nor the library, so it has not touched a GPU) and starts `python -m torch.distributed.run --nproc-per-node N bench.py ...`
@@ -349,10 +406,10 @@ def main():
         synthetic.contig_bytes_range(n, args.length, seed, lo, hi)
     d_seq = torch.from_numpy(seq).to(dev)
     d_off = torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    ctx.count_profiles(d_seq, d_off, args.pattern, "both")          # untimed first call (allocations)
+    my_counts, my_totals = ctx.count_profiles(d_seq, d_off, args.pattern, "both")     # untimed first call (allocations)
     torch.cuda.synchronize(dev)
     stage1_ms = None
-    for _ in range(3):                                               # best of 3, like every other line of the record
+    for _ in range(3 if args.full else 0):                           # best of 3, like every other line of the record
         t0 = time.perf_counter()
         my_counts, my_totals = ctx.count_profiles(d_seq, d_off, args.pattern, "both")
         torch.cuda.synchronize(dev)
@@ -409,6 +466,33 @@ def main():
         dist.all_reduce(one)                                   # every rank that took part adds 1
         ranks_seen = int(one.item())
         assert ranks_seen == dist.get_world_size() == world
+    if args.dump_outputs:                # the slab still holds what the last timed step wrote
+        dump_outputs(args.dump_outputs, plan, rank, slab, mirrors)
+
+    pairs = n * (n - 1) / 2.0
+    ms_per_step = elapsed / args.steps * 1e3
+    workload = ("%s: %d synthetic contigs x %d bp (seed %d), pattern %s both strands, -d %s, float64 matrix resident in HBM"
+                % (cfg_name, n, args.length, seed, args.pattern, args.metric))
+    result = {
+        "metric": "contig-pairs/sec", "value": pairs / (elapsed / args.steps), "unit": "pairs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak" if world == 1 else "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": workload, "contigs": n, "dim": dim, "pairs": pairs, "sharding": plan.describe(),
+                   "matrix_wall_ms": ms_per_step, "env_knobs": knobs},
+    }
+    if dist is not None:
+        result["config"]["multi_gpu"] = {
+            "ranks_seen": ranks_seen, "backend": "gloo (rehearsal on one GPU)" if rehearsal else "nccl (RCCL)",
+            "allgather_ms": allgather_ms, "allgather_bytes": int(counts.numel() * 4 + totals.numel() * 8)}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        ctx.close()
+        return
 
     # dominant kernel: HIP-event time of the tile kernels on the launch stream (every rank, averaged)
     kms = []
@@ -423,8 +507,6 @@ def main():
         dist.all_gather(g, torch.tensor([kernel_ms], dtype=torch.float64, device=cdev))
         rank_kernel_ms = [float(x.item()) for x in g]
 
-    pairs = n * (n - 1) / 2.0
-    ms_per_step = elapsed / args.steps * 1e3
     if rank == 0:
         main_kernel_id = st["kernel_id"]
         rc_folded = bool(st.get("rc_folded", False))
@@ -485,24 +567,15 @@ def main():
                                                 traffic=traffic_all.get("JSD_general_n%d_d%d" % (n, dim))),
                        "what": "valu_tile_kernel<JSD>: the kernel a ragged real assembly gets (totals differ inside every "
                                "128-record block, or counts above 127)"}
-        workload = ("%s: %d synthetic contigs x %d bp (seed %d), pattern %s both strands, -d %s, float64 matrix resident in HBM"
-                    % (cfg_name, n, args.length, seed, args.pattern, args.metric))
-        result = {
-            "metric": "contig-pairs/sec", "value": pairs / (elapsed / args.steps), "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak" if world == 1 else "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": workload, "contigs": n, "dim": dim, "pairs": pairs, "sharding": plan.describe(),
-                       "stage1_profile_ms": stage1_ms, "matrix_wall_ms": ms_per_step,
-                       "rc_folded": rc_folded,      # strand-symmetric profiles summed over one word per {w, rc(w)} orbit
-                       "equal_total_table_path": main_kernel_id == 6,
-                       "table_path_needs": "every 128-record block to share one word total and counts <= 127 (fixed-length "
-                                           "contigs, windows, reads; counts 128 .. 255 take the table's wide layout at ~1.4 x the "
-                                           "time); otherwise jsd_general_kernel_only is the rate",
-                       "jsd_general_kernel_only": general,
-                       "env_knobs": knobs},
-            "roofline": roof,
-        }
+        result["config"].update({
+            "stage1_profile_ms": stage1_ms,
+            "rc_folded": rc_folded,      # strand-symmetric profiles summed over one word per {w, rc(w)} orbit
+            "equal_total_table_path": main_kernel_id == 6,
+            "table_path_needs": "every 128-record block to share one word total and counts <= 127 (fixed-length "
+                                "contigs, windows, reads; counts 128 .. 255 take the table's wide layout at ~1.4 x the "
+                                "time); otherwise jsd_general_kernel_only is the rate",
+            "jsd_general_kernel_only": general})
+        result["roofline"] = roof
         if general is not None:      # the rate a ragged assembly gets, next to the headline (which needs equal totals)
             result["value_general_kernel"] = general["pairs_per_s"]
             result["value_general_kernel_note"] = ("same matrix through valu_tile_kernel<JSD> only; `value` is the integer-sum table "
@@ -514,15 +587,13 @@ def main():
                 rp = float(plan.pair_evaluations(r))
                 per_rank.append(dict(hbm_roofline(bytes_per_pair * rp, ms_r), rank=r, pairs=rp, kernel_ms=ms_r))
             result["roofline_per_rank"] = per_rank
-            result["config"]["multi_gpu"] = {
-                "ranks_seen": ranks_seen, "backend": "gloo (rehearsal on one GPU)" if rehearsal else "nccl (RCCL)",
-                "allgather_ms": allgather_ms, "allgather_bytes": int(counts.numel() * 4 + totals.numel() * 8),
+            result["config"]["multi_gpu"].update({
                 "complete_rows_ms": complete_rows_ms,
                 "kernel_ms_min": min(rank_kernel_ms), "kernel_ms_max": max(rank_kernel_ms), "kernel_ms_per_rank": rank_kernel_ms,
                 "pairs_rank0": rank_pairs,
                 "environment": __import__("phyloligo_amd.dist", fromlist=["dist_environment"]).dist_environment(),
                 "note": "all-gather = the single exchange of the path, outside the timed region like stage 1; "
-                        "complete_rows = optional second exchange delivering mirror blocks to row owners, not part of `value`"}
+                        "complete_rows = optional second exchange delivering mirror blocks to row owners, not part of `value`"})
         if world == 1 and args.metric == "JSD" and n == 50000 and not args.no_other_configs:
             # the other single-GPU BASELINE configurations, timed the same way (not part of `value`)
             others = {}

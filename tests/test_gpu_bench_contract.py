@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--contigs", "3000", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--contigs", "3000", "--steps", "2", "--warmup", "1",
+                          "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -61,7 +62,7 @@ def test_bench_multi_rank_path_rehearsal():
     env = dict(os.environ, PO_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--contigs", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                          "--gpus", "2", "--contigs", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -82,7 +83,7 @@ def test_bench_record_survives_an_exchange_that_does_not_complete():
     env = dict(os.environ, PO_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29537", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--contigs", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                          "--gpus", "2", "--contigs", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--complete-rows-timeout", "0.001"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -102,7 +103,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--contigs", "4096", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                          "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -138,3 +139,44 @@ def test_bench_default_workloads_are_the_baseline_configs():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'n, cfg_name, seed = 50000, "BASELINE config 2", synthetic.SEEDS["C2"]' in src
     assert 'n, cfg_name, seed = 200000, "BASELINE config 4", synthetic.SEEDS["C4"]' in src
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """The plain run - set-up, warm-up, --steps timed steps, one line with the headline figures and none of --full's - and
+    --dump-outputs: what the last step computed, a seeded sample of the float64 matrix, checked against the CPU oracle."""
+    import numpy as np
+    import torch
+    import bench
+    from oracle import phyloligo_oracle as po
+    from phyloligo_amd import synthetic
+    n = 3000
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--contigs", str(n), "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["metric"] == "contig-pairs/sec" and r["unit"] == "pairs/s" and r["higher_is_better"] is True and r["dtype"] == "f64"
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["n_gpus"] == 1 and r["config"]["pairs"] == n * (n - 1) / 2.0
+    assert abs(r["value"] - r["config"]["pairs"] / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+    for key in ("roofline", "cpu_baseline", "value_general_kernel", "value_ragged_assembly"):
+        assert key not in r, key
+    for key in ("ragged_assembly", "path_lines", "other_configs", "jsd_general_kernel_only", "stage1_profile_ms"):
+        assert key not in r["config"], key
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["distances_entries.npy", "distances_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    got = {f[len("distances_"):-len(".npy")]: np.load(tmp_path / f) for f in files}
+    # where each sampled value sits in the matrix: the same sampling over a matrix of positions
+    pos = dict(bench.sample_matrix(torch.arange(n * n, dtype=torch.float64).reshape(n, n), bench.DUMP_BUDGET_BYTES,
+                                   np.random.default_rng([0, 0])))
+    assert {k: v.shape for k, v in got.items()} == {k: v.shape for k, v in pos.items()}
+    assert all(v.dtype == np.float64 for v in got.values())
+    seq, offsets = synthetic.contig_bytes(n, 2000, seed=synthetic.SEEDS["C2"])
+    counts, totals = po.compute_counts([seq[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(n)], "1111", "both")
+    freq = po.counts_to_frequencies(counts, totals)
+    rows = (pos["rows"][:4, 0] // n).astype(np.int64)
+    np.testing.assert_allclose(got["rows"][:4], po.pairwise_rows(freq, "JSD", rows), rtol=1e-6, atol=1e-12)
+    flat = pos["entries"][:2000].astype(np.int64)
+    want = np.array([po.JSD(freq[i], freq[j]) for i, j in zip(flat // n, flat % n)])
+    np.testing.assert_allclose(got["entries"][:2000], want, rtol=1e-6, atol=1e-12)

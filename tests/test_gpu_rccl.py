@@ -36,7 +36,7 @@ def test_bench_over_rccl_one_rank():
     env = _env(29543)
     env["PO_BENCH_FORCE_DIST"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--contigs", "4096", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline", "--no-other-configs"],
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
