@@ -228,6 +228,37 @@ int po_pairwise_blocks_dev(po_ctx* ctx, const uint32_t* d_counts, const uint64_t
                            int metric, int out_dtype, const po_block* blocks, uint32_t n_blocks, uint32_t flags,
                            po_stats* stats);
 
+/* ---- k nearest neighbours: a sparse graph instead of the dense matrix ------------------------------------------------ *
+ * The reference hands the whole matrix to its next step (phyloselect.py reads it with numpy.loadtxt / a memmap and gives it to
+ * t-SNE with metric="precomputed", which only looks at the 3 perplexity + 1 nearest neighbours of each point; HDBSCAN's core
+ * distance is one neighbour).  These entry points select, for every record i of the n given, its k_eff = min(k, n - 1) nearest
+ * records j != i from the matrix po_pairwise_dev computes for the same input, metric and out dtype (val_dtype): v[i][j] below is
+ * bit for bit that matrix's (i, j) entry.  The matrix is evaluated panel by panel on the device and never leaves it whole.
+ *   idx int32 [n][k_eff]   val [n][k_eff] (float64 / float32)      row i in this order:
+ *     ascending v (PO_KT: descending, Kendall's tau is a similarity), NaN after every number, equal values by the smaller j
+ *   i.e. numpy.argsort(key, kind="stable")[:k_eff] over row i without its diagonal, key = v (-v for KT), NaN last.
+ * k: 1 .. 1024 (else PO_EINVAL); n <= 1 gives an empty result.  panel_rows: rows per panel, a multiple of 128 (0 = the slab and
+ * mirror of a panel near 256 MiB); the result does not depend on it.  The panel workspace is held by the context (po_ctx_trim).
+ * flags: those of po_pairwise* (PO_FLAG_NO_SYMMETRY is ignored: every pair is evaluated once, as in the dense symmetric path).
+ * stats: prep_ms and total_ms as po_pairwise*; kernel_ms is the tile kernels alone, the selection is total - prep - kernel.  */
+#define PO_KNN_MAX_K 1024u
+int po_knn(po_ctx* ctx, const uint32_t* counts, const uint64_t* totals, uint64_t n, uint32_t dim, int metric, uint32_t k,
+           int val_dtype, uint64_t panel_rows, int32_t* idx, void* val, uint32_t flags, po_stats* stats);
+int po_knn_dev(po_ctx* ctx, const uint32_t* d_counts, const uint64_t* d_totals, uint64_t n, uint32_t dim, int metric, uint32_t k,
+               int val_dtype, uint64_t panel_rows, int32_t* d_idx, void* d_val, uint32_t flags, po_stats* stats);
+/* The same over a work list of blocks of the matrix (a rank's share, as a multi-GPU plan deals it; out / mirror / ld_* of the
+ * blocks are ignored, row_begin / col_begin must be multiples of 128): a triangular block feeds both directions within itself,
+ * a rectangular block (rows and columns disjoint) feeds its rows, and its columns through the transposed copy.  The lists
+ * [n][k_eff] cover all n rows and are emptied first (idx -1 = unused entry): they are partial when the blocks do not cover the
+ * matrix, and po_knn_merge_dev combines the partial lists of several work lists.                                            */
+int po_knn_blocks_dev(po_ctx* ctx, const uint32_t* d_counts, const uint64_t* d_totals, uint64_t n, uint32_t dim, int metric,
+                      uint32_t k, int val_dtype, uint64_t panel_rows, const po_block* blocks, uint32_t n_blocks, int32_t* d_idx,
+                      void* d_val, uint32_t flags, po_stats* stats);
+/* m lists of shape [n][k] (idx_in / val_in: [m][n][k], each ordered as above, from disjoint pairs) -> one list [n][k] of the
+ * best k of each row, same order.  The reduction of a multi-rank k-NN run; metric gives the direction (PO_KT descending).     */
+int po_knn_merge_dev(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* d_idx_in, const void* d_val_in,
+                     uint32_t m, int32_t* d_idx, void* d_val);
+
 /* bytes of device workspace po_pairwise_dev will hold for this problem (allocated lazily on
  * first use and kept by the context; call once before timing to keep hipMalloc out of it)    */
 int po_pairwise_reserve(po_ctx* ctx, uint64_t n, uint32_t dim, int metric);

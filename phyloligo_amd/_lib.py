@@ -33,6 +33,7 @@ PO_FLAG_NO_TABLE_PATH = 2
 PO_FLAG_NO_RC_FOLD = 4
 PO_FLAG_PAIRDOT_I8 = 8
 PO_FLAG_NO_PAIRDOT = 16
+PO_KNN_MAX_K = 1024
 
 
 class PoStats(ctypes.Structure):
@@ -86,6 +87,11 @@ SIGNATURES = {
     "po_pairwise_freq_dev": (_int, [_vp, _vp, _u64, _u32, _int, _u64, _u64, _int, _vp, _u64, _u32, _c.POINTER(PoStats)]),
     "po_pairwise_blocks_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _int, _c.POINTER(PoBlock), _u32, _u32, _c.POINTER(PoStats)]),
     "po_pairwise_reserve": (_int, [_vp, _u64, _u32, _int]),
+    "po_knn": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _u32, _int, _u64, _vp, _vp, _u32, _c.POINTER(PoStats)]),
+    "po_knn_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _u32, _int, _u64, _vp, _vp, _u32, _c.POINTER(PoStats)]),
+    "po_knn_blocks_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _u32, _int, _u64, _c.POINTER(PoBlock), _u32, _vp, _vp, _u32,
+                                 _c.POINTER(PoStats)]),
+    "po_knn_merge_dev": (_int, [_vp, _u64, _u32, _int, _int, _vp, _vp, _u32, _vp, _vp]),
     "po_fasta_scan": (_int, [_vp, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),
     "po_fasta_extract": (_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
     "po_file_read": (_int, [_cp, _vp, _u64]),

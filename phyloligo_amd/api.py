@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PoBlock, PoStats,
+from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoStats,
                    check)
 
 
@@ -259,6 +259,90 @@ class Context:
                     "rc_folded": bool(stats.rc_folded)}
         return None
 
+    # ---- k nearest neighbours -----------------------------------------------------------------
+    def knn(self, counts, totals, k, metric="JSD", dtype="float64", panel_rows=0, want_stats=False, table_path=True,
+            rc_fold=True):
+        """The k_eff = min(k, n - 1) nearest records of every record: idx int32 [n, k_eff], val [n, k_eff] (po_knn*), ordered
+        by value (descending for KT), NaN last, ties by the smaller index; val[i, c] is the entry (i, idx[i, c]) of
+        pairwise(counts, totals, metric, dtype=dtype) bit for bit.  numpy in -> numpy out; torch CUDA tensors in -> tensors out.
+        Returns (idx, val), or (idx, val, stats) with want_stats (stats["select_ms"]: the selection kernels)."""
+        code, k, f32 = _knn_args(metric, k, dtype)
+        n, dim = counts.shape
+        k_eff = min(k, max(n - 1, 0))
+        flags = (0 if table_path else PO_FLAG_NO_TABLE_PATH) | (0 if rc_fold else PO_FLAG_NO_RC_FOLD)
+        stats = PoStats()
+        sp = ctypes.byref(stats) if want_stats else None
+        if _is_torch(counts):
+            import torch
+            self._check_device(counts, totals)
+            assert counts.dtype == torch.int32 and totals.dtype == torch.int64
+            assert counts.is_contiguous() and totals.is_contiguous()
+            idx = torch.empty((n, k_eff), dtype=torch.int32, device=counts.device)
+            val = torch.empty((n, k_eff), dtype=torch.float32 if f32 else torch.float64, device=counts.device)
+            self._use_torch_stream()
+            check(self._lib.po_knn_dev(self._h, counts.data_ptr(), totals.data_ptr(), n, dim, code, k, PO_F32 if f32 else PO_F64,
+                                       int(panel_rows), idx.data_ptr(), val.data_ptr(), flags, sp))
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+            totals = np.ascontiguousarray(totals, dtype=np.uint64)
+            idx = np.zeros((n, k_eff), dtype=np.int32)
+            val = np.zeros((n, k_eff), dtype=np.float32 if f32 else np.float64)
+            check(self._lib.po_knn(self._h, _np_ptr(counts), _np_ptr(totals), n, dim, code, k, PO_F32 if f32 else PO_F64,
+                                   int(panel_rows), _np_ptr(idx), _np_ptr(val), flags, sp))
+        if want_stats:
+            return idx, val, _knn_stats(stats)
+        return idx, val
+
+    def knn_blocks(self, counts, totals, k, blocks, metric="JSD", dtype="float64", panel_rows=0, want_stats=False):
+        """Partial lists [n, k_eff] from a work list of blocks (device tensors; po_knn_blocks_dev).  `blocks`: dicts with
+        rows=(lo, hi), cols=(lo, hi), optional triangular=True - or the (rows, cols, kind, peer) items of RowBlockPlan.work(rank).
+        Returns (idx, val); idx -1 marks an entry no pair of the blocks filled."""
+        import torch
+        code, k, f32 = _knn_args(metric, k, dtype)
+        self._check_device(counts, totals)
+        assert counts.dtype == torch.int32 and totals.dtype == torch.int64 and counts.is_contiguous() and totals.is_contiguous()
+        n, dim = counts.shape
+        k_eff = min(k, max(n - 1, 0))
+        arr = (PoBlock * max(1, len(blocks)))()
+        for q, b in zip(arr, blocks):
+            if isinstance(b, dict):
+                rows, cols, tri = b["rows"], b["cols"], bool(b.get("triangular"))
+            else:
+                rows, cols, tri = b[0], b[1], b[2] == "diag"
+            (q.row_begin, q.row_end), (q.col_begin, q.col_end) = rows, cols
+            q.triangular = 1 if tri else 0
+        idx = torch.empty((n, k_eff), dtype=torch.int32, device=counts.device)
+        val = torch.empty((n, k_eff), dtype=torch.float32 if f32 else torch.float64, device=counts.device)
+        stats = PoStats()
+        self._use_torch_stream()
+        check(self._lib.po_knn_blocks_dev(self._h, counts.data_ptr(), totals.data_ptr(), n, dim, code, k, PO_F32 if f32 else PO_F64,
+                                          int(panel_rows), arr, len(blocks), idx.data_ptr(), val.data_ptr(), 0,
+                                          ctypes.byref(stats) if want_stats else None))
+        if want_stats:
+            return idx, val, _knn_stats(stats)
+        return idx, val
+
+    def knn_merge(self, idx_lists, val_lists, metric="JSD"):
+        """Merge m partial lists (device tensors [n, k] each, or stacked [m, n, k]) into one [n, k] (po_knn_merge_dev)."""
+        import torch
+        idx_in = idx_lists if _is_torch(idx_lists) else torch.stack(list(idx_lists))
+        val_in = val_lists if _is_torch(val_lists) else torch.stack(list(val_lists))
+        idx_in, val_in = idx_in.contiguous(), val_in.contiguous()
+        assert idx_in.dim() == 3 and idx_in.shape == val_in.shape and idx_in.dtype == torch.int32
+        assert val_in.dtype in (torch.float32, torch.float64)
+        m, n, k = idx_in.shape
+        f32 = val_in.dtype == torch.float32
+        code, _, _ = _knn_args(metric, max(k, 1), "float32" if f32 else "float64")
+        self._check_device(idx_in, val_in)
+        idx = torch.empty((n, k), dtype=torch.int32, device=idx_in.device)
+        val = torch.empty((n, k), dtype=val_in.dtype, device=idx_in.device)
+        if k == 0 or n == 0:
+            return idx, val
+        self._use_torch_stream()
+        check(self._lib.po_knn_merge_dev(self._h, n, k, code, PO_F32 if f32 else PO_F64, idx_in.data_ptr(), val_in.data_ptr(), m,
+                                         idx.data_ptr(), val.data_ptr()))
+        return idx, val
+
     def _pairwise(self, counts, totals, freq, metric, row_begin, row_end, dtype, symmetric, out, want_stats,
                   extra_flags=0):
         if metric not in METRICS:
@@ -319,6 +403,61 @@ class Context:
                          "pairs": stats.pairs, "tiles": stats.tiles, "kernel_id": stats.kernel_id,
                     "rc_folded": bool(stats.rc_folded)}
         return out
+
+
+def check_knn_k(k):
+    """k of the k-NN entry points: an integer in 1..1024 (PO_EINVAL otherwise, as the library answers)"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= PO_KNN_MAX_K:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "k must be an integer in 1..%d (got %r)" % (PO_KNN_MAX_K, k))
+    return int(k)
+
+
+def _knn_args(metric, k, dtype):
+    if metric not in METRICS:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "unknown metric %r" % (metric,))
+    return METRICS[metric], check_knn_k(k), str(dtype) in ("float32", "torch.float32", "f32")
+
+
+def _knn_stats(stats):
+    return {"prep_ms": stats.prep_ms, "kernel_ms": stats.kernel_ms, "total_ms": stats.total_ms,
+            "select_ms": max(0.0, stats.total_ms - stats.prep_ms - stats.kernel_ms), "pairs": stats.pairs,
+            "tiles": stats.tiles, "kernel_id": stats.kernel_id, "rc_folded": bool(stats.rc_folded)}
+
+
+def knn_self_values(metric, val, totals=None, counts=None):
+    """The diagonal of the dense matrix for every record (what write_knn_npz puts first in each row): 0, except KT, whose
+    diagonal is 1 - or 0 for a record whose profile is constant (all words tied)."""
+    n = val.shape[0]
+    out = np.zeros(n, dtype=val.dtype)
+    if metric == "KT":
+        c = np.asarray(counts)
+        out[:] = 1
+        if n:
+            out[(c == c[:, :1]).all(axis=1)] = 0
+    return out
+
+
+def write_knn_npz(path, idx, val, self_value):
+    """The k-NN graph as the CSR container scipy.sparse.save_npz writes (keys data, indices, indptr, format, shape): row i
+    holds i itself with self_value (a scalar or one value per row: the dense diagonal) and then its neighbours in order.
+    Written to exactly `path` (a file object, so that numpy does not append ".npz"); no scipy needed."""
+    idx = np.asarray(idx)
+    val = np.asarray(val)
+    n, k = idx.shape
+    data = np.empty((n, k + 1), dtype=val.dtype)
+    indices = np.empty((n, k + 1), dtype=np.int32)
+    data[:, 0] = self_value
+    data[:, 1:] = val
+    indices[:, 0] = np.arange(n, dtype=np.int32)
+    indices[:, 1:] = idx
+    indptr = np.arange(0, n * (k + 1) + 1, k + 1, dtype=np.int32 if n * (k + 1) < 2 ** 31 else np.int64)
+    import zipfile
+    # numpy.savez's layout (one .npy member per key, stored) with a fixed member time stamp: the same graph gives the same bytes
+    with open(path, "wb") as fh, zipfile.ZipFile(fh, mode="w", compression=zipfile.ZIP_STORED, allowZip64=True) as zf:
+        for key, arr in (("indices", indices.reshape(-1)), ("indptr", indptr), ("format", np.array("csr")),
+                         ("shape", np.array([n, n], dtype=np.int64)), ("data", data.reshape(-1))):
+            with zf.open(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w", force_zip64=True) as fid:
+                np.lib.format.write_array(fid, np.asanyarray(arr), allow_pickle=False)
 
 
 # ---- host formats -------------------------------------------------------------------------------

@@ -75,6 +75,7 @@ struct po_ctx {
     size_t h_blockmax_cap = 0;         // in words
     po_buf ws_tilelist;                // per-class tile lists of the int8 Gram path (po_gram_i8.hip)
     po_buf ws_fix;                     // po_fix_list of the JSD path (po_jsd_exact.hip)
+    po_buf ws_knn;                     // panel slab + mirror of the k-NN drivers (po_knn*): grown once per call shape
     void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of the host-pointer entry points (device -> host rows)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
@@ -265,5 +266,19 @@ int po_launch_kt_panel_prep(po_ctx* ctx, const uint32_t* d_lessrank, uint64_t n,
                             const uint32_t* fold_src, uint32_t fold_src_len, uint32_t n_selfs, uint32_t n_pairs,
                             po_kt_panel_plan* plan);
 int po_launch_kt_panel_tiles(po_ctx* ctx, const po_tile_args& a, const void* ws, const po_kt_panel_plan& plan, uint64_t* tiles);
+
+// K nearest neighbours (po_knn.hip): one batch of candidate rows merged into the sorted lists idx int32 [n][k] / val [n][k]
+struct po_knn_batch {
+    const void* src;          // candidate row t: src + t * ld (elements of the value type), len values
+    uint64_t ld;
+    const int32_t* cidx;      // NULL: the candidate columns are col0 + 0 .. len-1; else cidx + t * ldc (the merge; -1 = none)
+    uint64_t ldc;
+    uint64_t row0, rows;      // list rows fed: row0 .. row0 + rows
+    uint32_t len, col0;
+    int diag;                 // column == row is not a candidate
+};
+size_t po_knn_select_shmem(uint32_t k, int val_f32);
+// desc: Kendall's tau (descending order); val_f32: the lists and candidates are float32 (else float64)
+int po_launch_knn_select(po_ctx* ctx, int32_t* d_idx, void* d_val, uint32_t k, int val_f32, int desc, const po_knn_batch& b);
 
 static inline uint64_t po_round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }

@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 from . import api
-from ._lib import METRICS, STRANDS
+from ._lib import METRICS, PO_KNN_MAX_K, STRANDS
 
 _ctx = None
 LAST_STAGE2 = None       # PoStats of the first stage-2 call of the last compute_distances() (what --json-stats reports)
@@ -391,9 +391,30 @@ def get_cmd(argv=None):
     parser.add_argument("--gpus", action="store", dest="gpus", type=int, default=1,
                         help="not in the reference: GPUs of this node to use, one process each (python -m phyloligo_amd starts "
                              "the ranks itself; the analogue of the reference fanning out to -c joblib workers) [default:%(default)d]")
+    parser.add_argument("--knn", action="store", dest="knn", type=int, default=None, metavar="K",
+                        help="not in the reference: write the K nearest neighbours of every contig (1 <= K <= 1024) to -o as a "
+                             "sparse CSR graph (scipy.sparse.load_npz reads it; row i: i itself, then its neighbours by distance) "
+                             "instead of the N x N matrix; float64 values")
     params = parser.parse_args(argv)
     params.workdir = os.path.abspath(params.workdir)
     return params
+
+
+def _knn_refused(params):
+    """the reason --knn cannot run with these options, or None"""
+    if params.knn is None:
+        return None
+    if not 1 <= params.knn <= PO_KNN_MAX_K:
+        return "Error, --knn K needs 1 <= K <= %d (got %d)" % (PO_KNN_MAX_K, params.knn)
+    if params.large != "None":
+        return "Error, --knn writes a neighbour graph, not a matrix container: it cannot be combined with --large %s" % params.large
+    if params.mthdrun not in ("joblib", "hip"):
+        return "Error, --knn supports --method joblib|hip"
+    return None
+
+
+def _write_knn(params, counts, idx, val):
+    api.write_knn_npz(params.out_file, idx, val, api.knn_self_values(params.dist, val, counts=counts))
 
 
 def main_distributed(params):
@@ -423,6 +444,10 @@ def main_distributed(params):
                 print("Error, --large h5py needs libhdf5 (>= 1.10), which was not found on this system", file=sys.stderr)
             sys.exit(1)
     if params.strand not in STRANDS or params.dist not in METRICS:
+        sys.exit(1)
+    if _knn_refused(params):
+        if rank == 0:
+            print(_knn_refused(params), file=sys.stderr)
         sys.exit(1)
     from .dist import first_contact
     first_contact("cuda.set_device", torch.cuda.set_device, local)
@@ -463,6 +488,8 @@ def main_distributed(params):
         counts, totals = first_contact("all_gather_profiles", gather)
     say("Computing Pairwise distances")
     t_dist0 = time.perf_counter()
+    if params.knn is not None:
+        return _knn_distributed(params, ctx, plan, rank, world, counts, totals, rehearsal, tdist, t_start, t_dist0)
     dtype = torch.float32 if params.large in ("memmap", "h5py") else torch.float64
     slab, mirrors = plan.allocate(rank, dev, dtype)
     plan.compute(ctx, counts, totals, params.dist, rank, slab, mirrors)
@@ -555,12 +582,48 @@ def main_distributed(params):
     return 0
 
 
+def _knn_distributed(params, ctx, plan, rank, world, counts, totals, rehearsal, tdist, t_start, t_dist0):
+    """--knn on several GPUs: every rank selects from the blocks of its tournament work list (partial lists over all n rows),
+    rank 0 gathers the lists, merges them and writes the graph.  No row-completing exchange: the lists are [n, K], not rows."""
+    import torch
+    global LAST_STAGE2
+    n = int(counts.shape[0])
+    idx, val, st = ctx.knn_blocks(counts, totals, params.knn, plan.work(rank), params.dist, "float64", want_stats=True)
+    torch.cuda.synchronize()
+    t_computed = time.perf_counter()
+    if rehearsal:                                               # gloo moves host tensors
+        idx, val = idx.cpu(), val.cpu()
+    idx_all = [torch.empty_like(idx) for _ in range(world)]
+    val_all = [torch.empty_like(val) for _ in range(world)]
+    tdist.all_gather(idx_all, idx)
+    tdist.all_gather(val_all, val)
+    if params.out_freq_file and rank == 0:
+        print("Writing frequency matrix")
+        api.write_mat_text(params.out_freq_file, ctx.frequencies(counts, totals).cpu().numpy())
+    if rank == 0:
+        print("Writing distance matrix")
+        dev = counts.device
+        m_idx, m_val = ctx.knn_merge(torch.stack(idx_all).to(dev), torch.stack(val_all).to(dev), params.dist)
+        _write_knn(params, counts.cpu().numpy(), m_idx.cpu().numpy(), m_val.cpu().numpy())
+        LAST_STAGE2 = dict(st, rows=[0, n])
+        if params.json_stats:
+            t_end = time.perf_counter()
+            _write_json_stats(params, _Shape(n, int(counts.shape[1])), t_dist0 - t_start, t_computed - t_dist0, t_end - t_computed,
+                              t_end - t_start, gpus=world)
+    tdist.barrier()
+    tdist.destroy_process_group()
+    return 0
+
+
 def main(argv=None):
     params = get_cmd(argv)
     if type(params.pattern) == int:                      # :1040-1041
         params.pattern = str("1") * params.pattern
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return main_distributed(params)
+    if _knn_refused(params):
+        print(_knn_refused(params), file=sys.stderr)
+        sys.exit(1)
     t_start = time.perf_counter()
     print("Using pattern {}".format(params.pattern))
     if not os.path.isdir(params.workdir):
@@ -574,6 +637,8 @@ def main(argv=None):
     t_freq = time.perf_counter()
     print("Computing Pairwise distances")
     t_dist0 = time.perf_counter()
+    if params.knn is not None:
+        return _knn_single(params, frequencies, t_start, t_freq, t_dist0)
     res = compute_distances(params.mthdrun, params.large, frequencies, freq_name, params.out_file, params.dist,
                             params.threads_max, params.freqchunksize, params.workdir)
     t_dist = time.perf_counter()
@@ -586,6 +651,30 @@ def main(argv=None):
         if res is not None:                  # None: unknown --method, nothing was computed (:552 only prints)
             api.write_mat_text(params.out_file, res)
     if params.json_stats and frequencies is not None:
+        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
+    return 0
+
+
+def _knn_single(params, frequencies, t_start, t_freq, t_dist0):
+    """--knn in one process: the graph from the integer profiles (po_knn, float64), written to -o"""
+    global LAST_STAGE2
+    if frequencies is None:
+        return 0
+    if params.dist not in METRICS:
+        print("Error, unknown metric methodfor joblib: {}".format(params.dist), file=sys.stderr)
+        sys.exit(1)
+    counts, totals = frequencies.counts, frequencies.totals
+    n = frequencies.shape[0]
+    idx, val, st = _context().knn(counts, totals, params.knn, params.dist, "float64", want_stats=True)
+    LAST_STAGE2 = dict(st, rows=[0, n])
+    t_dist = time.perf_counter()
+    _timing("single process: k-NN graph %.3f s" % (t_dist - t_dist0))
+    if params.out_freq_file:
+        print("Writing frequency matrix")
+        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
+    print("Writing distance matrix")
+    _write_knn(params, counts, idx, val)
+    if params.json_stats:
         _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
     return 0
 
@@ -608,6 +697,8 @@ def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpu
              "seconds": {"frequencies": freq_s, "distances" + ("_and_container" if params.large in ("memmap", "h5py") else ""): dist_s,
                          "writing": write_s, "total": total_s},
              "stage2_first_call": LAST_STAGE2,
+             **({} if getattr(params, "knn", None) is None else
+                {"knn": params.knn, "knn_select_ms": None if LAST_STAGE2 is None else LAST_STAGE2.get("select_ms")}),
              "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
     with open(params.json_stats, "w") as fh:
         json.dump(stats, fh, indent=1)
