@@ -259,6 +259,62 @@ int po_knn_blocks_dev(po_ctx* ctx, const uint32_t* d_counts, const uint64_t* d_t
 int po_knn_merge_dev(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* d_idx_in, const void* d_val_in,
                      uint32_t m, int32_t* d_idx, void* d_val);
 
+/* ---- t-SNE of the k-NN graph: the 2-D map phyloselect.py clusters on ------------------------------------------------------ *
+ * Replaces transform_matrix_tsne (bin/phyloselect.py:381-398): sklearn.manifold.TSNE(n_components=2, random_state=0,
+ * perplexity=p, metric="precomputed") on the distance matrix.  t-SNE looks at the K = min(n - 1, int(3 p + 1)) nearest
+ * neighbours of every point only, so the lists of po_knn* are its whole input and the matrix never exists.  scikit-learn's
+ * algorithm (1.7: manifold/_t_sne.py, _utils.pyx) step for step, except that the repulsive force is summed exactly over all
+ * pairs (method="barnes_hut" with angle=0.0) and that init is "random".  Three steps, each an entry point of its own.
+ * The same inputs give the same bytes on every call.  The un-suffixed form takes host pointers.
+ *
+ * 1. po_tsne_affinities_dev: lists idx int32 [n][k] / val [n][k] (val_dtype; distances, squared here) -> per row the precision
+ *    beta [n] (float64, may be NULL) found by scikit-learn's binary search, the conditional probabilities cond float64 [n][k]
+ *    (may be NULL), and the joint probabilities P = (C + C^T) / sum(C + C^T) as CSR: rowptr int64 [n + 1], col int32 and
+ *    p float32 [*nnz], columns ascending in every row.  cap: entries col / p can hold; 2 n k is always enough, less gives
+ *    PO_EINVAL with the number needed in *nnz.  Synchronises the stream (validation and nnz are read back).
+ *    PO_EINVAL: perplexity < 1 or int(3 perplexity + 1) > PO_KNN_MAX_K; n < 4; k != min(n - 1, int(3 perplexity + 1));
+ *    metric PO_KT (a similarity, ordered descending); a NaN or negative value, or a neighbour index outside 0..n-1 or equal
+ *    to its row, or a neighbour listed twice in a row - checked on the device, the message names the first offending row.
+ * 2. po_tsne_gradient_dev: CSR P, embedding y float32 [n][2], exaggeration -> grad float32 [n][2] of the KL divergence
+ *    between exaggeration * P and Q, *z = sum over i != j of 1 / (1 + |y_i - y_j|^2) and *kl (host doubles, any may be NULL).
+ *    The CSR indexes y, so its row pointers and columns are checked on the device first (PO_EINVAL names the first bad row):
+ *    every call synchronises the stream once for that, and once more when z or kl is asked for.
+ * 3. po_tsne_dev: CSR P and the start y0 float32 [n][2] -> the embedding y float32 [n][2] after scikit-learn's
+ *    _gradient_descent.  A zero in po_tsne_params selects scikit-learn's value.  The CSR is checked as in 2. (one synchronisation
+ *    before the loop; po_tsne, which has just built it, skips that).  Every n_iter_check iterations KL and the gradient norm
+ *    are read back (the loop's only synchronisation).  Returns when y is complete.                        */
+typedef struct po_tsne_params {
+    uint32_t max_iter;                 /* 0: 1000 */
+    uint32_t exploration_iter;         /* 0: 250 iterations with early_exaggeration and momentum 0.5, then 1 and 0.8 */
+    uint32_t n_iter_check;             /* 0: 50 */
+    uint32_t n_iter_without_progress;  /* 0: 300 */
+    double early_exaggeration;         /* 0: 12 */
+    double learning_rate;              /* 0: max(n / early_exaggeration / 4, 50) */
+    double min_grad_norm;              /* 0: 1e-7 */
+    double* history;                   /* host, may be NULL: per check (iteration, KL, gradient norm), history_cap triples */
+    uint32_t history_cap;
+    uint32_t time_kernels;             /* != 0: device events around the kernels of every iteration (po_tsne_result *_ms below) */
+} po_tsne_params;
+typedef struct po_tsne_result {
+    double kl;                         /* KL divergence of the returned embedding (exaggeration 1) */
+    double grad_norm;                  /* gradient norm at the last check (0 if there was none) */
+    double z;                          /* sum of q over all pairs of the returned embedding */
+    uint32_t iterations;               /* update steps made */
+    uint32_t history_len;              /* checks made (entries written to history: min(history_len, history_cap)) */
+    double affinities_ms, optimise_ms; /* po_tsne only: HIP-event times of the two parts */
+    double repulsion_ms, attraction_ms, rest_ms; /* time_kernels: median per iteration of the repulsion kernel, of the attraction +
+                                          update kernel, and of the rest of an iteration (Z reduction, gaps between launches) */
+} po_tsne_result;
+int po_tsne_affinities_dev(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* d_idx, const void* d_val,
+                           double perplexity, double* d_beta, double* d_cond, int64_t* d_rowptr, int32_t* d_col, float* d_p,
+                           uint64_t cap, uint64_t* nnz);
+int po_tsne_gradient_dev(po_ctx* ctx, uint64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_p, uint64_t nnz,
+                         const float* d_y, double exaggeration, float* d_grad, double* z, double* kl);
+int po_tsne_dev(po_ctx* ctx, uint64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_p, uint64_t nnz,
+                const float* d_y0, const po_tsne_params* params, float* d_y, po_tsne_result* result);
+int po_tsne(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* idx, const void* val, double perplexity,
+            const float* y0, const po_tsne_params* params, float* y, po_tsne_result* result);
+
 /* bytes of device workspace po_pairwise_dev will hold for this problem (allocated lazily on
  * first use and kept by the context; call once before timing to keep hipMalloc out of it)    */
 int po_pairwise_reserve(po_ctx* ctx, uint64_t n, uint32_t dim, int metric);

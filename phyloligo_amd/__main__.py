@@ -18,6 +18,10 @@ try:
     _n = int(_gpus_asked(sys.argv[1:]))
 except ValueError:
     _n = 1                               # get_cmd() below reports the malformed value
+if _n > 1 and any(a == "--tsne" or a.startswith("--tsne=") for a in sys.argv[1:]):
+    # refused before any rank is started (phyloligo._tsne_refused says the same inside a rank)
+    sys.stderr.write("Error, --tsne runs on one GPU: an embedding over several ranks (--gpus N > 1) is out of scope\n")
+    sys.exit(1)
 if launch.needs_launcher(_n):
     # --gpus N > 1: this process only starts one rank per GPU (python -m torch.distributed.run ... -m phyloligo_amd <same
     # arguments>) and waits for them - the reference fans out to its own workers the same way (bin/phyloligo.py:386-390).

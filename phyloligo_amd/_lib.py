@@ -49,6 +49,20 @@ class PoBlock(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class PoTsneParams(ctypes.Structure):
+    """po_tsne_params: a zero selects scikit-learn's value"""
+    _fields_ = [("max_iter", ctypes.c_uint32), ("exploration_iter", ctypes.c_uint32), ("n_iter_check", ctypes.c_uint32),
+                ("n_iter_without_progress", ctypes.c_uint32), ("early_exaggeration", ctypes.c_double),
+                ("learning_rate", ctypes.c_double), ("min_grad_norm", ctypes.c_double), ("history", ctypes.POINTER(ctypes.c_double)),
+                ("history_cap", ctypes.c_uint32), ("time_kernels", ctypes.c_uint32)]
+
+
+class PoTsneResult(ctypes.Structure):
+    _fields_ = [("kl", ctypes.c_double), ("grad_norm", ctypes.c_double), ("z", ctypes.c_double), ("iterations", ctypes.c_uint32),
+                ("history_len", ctypes.c_uint32), ("affinities_ms", ctypes.c_double), ("optimise_ms", ctypes.c_double),
+                ("repulsion_ms", ctypes.c_double), ("attraction_ms", ctypes.c_double), ("rest_ms", ctypes.c_double)]
+
+
 class PhyloligoError(RuntimeError):
     def __init__(self, status, message):
         super().__init__("phyloligo_amd: %s (status %d)" % (message, status))
@@ -57,6 +71,7 @@ class PhyloligoError(RuntimeError):
 
 _c = ctypes
 _vp, _u64, _u32, _int, _cp = _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_int, _c.c_char_p
+_dbl = _c.c_double
 
 # name -> (restype, argtypes); every symbol include/phyloligo_amd.h declares
 SIGNATURES = {
@@ -92,6 +107,10 @@ SIGNATURES = {
     "po_knn_blocks_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _u32, _int, _u64, _c.POINTER(PoBlock), _u32, _vp, _vp, _u32,
                                  _c.POINTER(PoStats)]),
     "po_knn_merge_dev": (_int, [_vp, _u64, _u32, _int, _int, _vp, _vp, _u32, _vp, _vp]),
+    "po_tsne_affinities_dev": (_int, [_vp, _u64, _u32, _int, _int, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _u64, _c.POINTER(_u64)]),
+    "po_tsne_gradient_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _dbl, _vp, _c.POINTER(_dbl), _c.POINTER(_dbl)]),
+    "po_tsne_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _c.POINTER(PoTsneParams), _vp, _c.POINTER(PoTsneResult)]),
+    "po_tsne": (_int, [_vp, _u64, _u32, _int, _int, _vp, _vp, _dbl, _vp, _c.POINTER(PoTsneParams), _vp, _c.POINTER(PoTsneResult)]),
     "po_fasta_scan": (_int, [_vp, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),
     "po_fasta_extract": (_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
     "po_file_read": (_int, [_cp, _vp, _u64]),

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoStats,
+from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoStats, PoTsneParams, PoTsneResult,
                    check)
 
 
@@ -343,6 +343,106 @@ class Context:
                                          idx.data_ptr(), val.data_ptr()))
         return idx, val
 
+    # ---- t-SNE of the k-NN graph ---------------------------------------------------------------
+    def tsne_affinities(self, idx, val, perplexity, metric="Eucl"):
+        """scikit-learn's joint probabilities from the lists of knn() with k = tsne_neighbours(n, perplexity)
+        (po_tsne_affinities_dev): a dict with beta [n] and cond [n, k] (float64: the precision found per row and the
+        conditional probabilities), and the CSR of P = (C + C^T) / sum: rowptr int64 [n + 1], col int32 [nnz] (ascending in
+        every row), p float32 [nnz].  numpy in -> numpy out; torch CUDA tensors in -> tensors out."""
+        import torch
+        as_numpy = not _is_torch(idx)
+        if as_numpy:
+            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).cuda(self.device)
+            val = torch.from_numpy(np.ascontiguousarray(val)).cuda(self.device)
+        n, k = idx.shape
+        code, f32 = _tsne_list_args(metric, val, perplexity)
+        self._check_device(idx, val)
+        assert idx.dtype == torch.int32 and idx.is_contiguous() and val.is_contiguous() and val.shape == idx.shape
+        dev = idx.device
+        cap = 2 * n * k
+        beta = torch.empty((n,), dtype=torch.float64, device=dev)
+        cond = torch.empty((n, k), dtype=torch.float64, device=dev)
+        rowptr = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+        col = torch.empty((cap,), dtype=torch.int32, device=dev)
+        p = torch.empty((cap,), dtype=torch.float32, device=dev)
+        nnz = ctypes.c_uint64()
+        self._use_torch_stream()
+        check(self._lib.po_tsne_affinities_dev(self._h, n, k, code, PO_F32 if f32 else PO_F64, idx.data_ptr(), val.data_ptr(),
+                                               float(perplexity), beta.data_ptr(), cond.data_ptr(), rowptr.data_ptr(),
+                                               col.data_ptr(), p.data_ptr(), cap, ctypes.byref(nnz)))
+        out = {"beta": beta, "cond": cond, "rowptr": rowptr, "col": col[:nnz.value].clone(), "p": p[:nnz.value].clone()}
+        if as_numpy:
+            out = {key: t.cpu().numpy() for key, t in out.items()}
+        return out
+
+    def tsne_gradient(self, rowptr, col, p, y, exaggeration=1.0):
+        """Gradient of KL(exaggeration * P || Q) at the embedding y float32 [n, 2] (po_tsne_gradient_dev): (grad float32
+        [n, 2], Z, KL) with Z = sum over i != j of 1 / (1 + |y_i - y_j|^2), summed exactly over all pairs."""
+        import torch
+        as_numpy = not _is_torch(y)
+        if as_numpy:
+            rowptr, col, p, y = (torch.from_numpy(np.ascontiguousarray(a, dtype=t)).cuda(self.device)
+                                 for a, t in ((rowptr, np.int64), (col, np.int32), (p, np.float32), (y, np.float32)))
+        self._check_device(rowptr, col, p, y)
+        assert rowptr.dtype == torch.int64 and col.dtype == torch.int32 and p.dtype == torch.float32 and y.dtype == torch.float32
+        assert all(t.is_contiguous() for t in (rowptr, col, p, y)) and y.dim() == 2 and y.shape[1] == 2
+        n = y.shape[0]
+        assert rowptr.numel() == n + 1 and col.numel() == p.numel()
+        grad = torch.empty_like(y)
+        z, kl = ctypes.c_double(), ctypes.c_double()
+        self._use_torch_stream()
+        check(self._lib.po_tsne_gradient_dev(self._h, n, rowptr.data_ptr(), col.data_ptr(), p.data_ptr(), col.numel(), y.data_ptr(),
+                                             float(exaggeration), grad.data_ptr(), ctypes.byref(z), ctypes.byref(kl)))
+        return (grad.cpu().numpy() if as_numpy else grad), z.value, kl.value
+
+    def tsne_optimise(self, rowptr, col, p, y0, max_iter=1000, exploration_iter=None, want_stats=False, time_kernels=False):
+        """scikit-learn's gradient descent from y0 on the CSR of tsne_affinities (po_tsne_dev; device tensors).  time_kernels:
+        the stats carry repulsion_ms / attraction_ms / rest_ms, medians per iteration from device events."""
+        import torch
+        self._check_device(rowptr, col, p, y0)
+        assert rowptr.dtype == torch.int64 and col.dtype == torch.int32 and p.dtype == torch.float32 and y0.dtype == torch.float32
+        assert all(t.is_contiguous() for t in (rowptr, col, p, y0)) and y0.dim() == 2 and y0.shape[1] == 2
+        n = y0.shape[0]
+        assert rowptr.numel() == n + 1 and col.numel() == p.numel()
+        params, hist = _tsne_params(max_iter, exploration_iter)
+        params.time_kernels = 1 if time_kernels else 0
+        res = PoTsneResult()
+        y = torch.empty_like(y0)
+        self._use_torch_stream()
+        check(self._lib.po_tsne_dev(self._h, n, rowptr.data_ptr(), col.data_ptr(), p.data_ptr(), col.numel(), y0.data_ptr(),
+                                    ctypes.byref(params), y.data_ptr(), ctypes.byref(res)))
+        return (y, _tsne_stats(res, hist)) if want_stats else y
+
+    def tsne(self, idx, val, perplexity, seed=0, max_iter=1000, y0=None, want_stats=False, metric="Eucl", exploration_iter=None):
+        """The 2-D t-SNE embedding float32 [n, 2] of the points whose k = tsne_neighbours(n, perplexity) nearest neighbours
+        knn() listed: what sklearn.manifold.TSNE(n_components=2, perplexity=perplexity, metric="precomputed", init="random",
+        random_state=seed, method="barnes_hut", angle=0.0) computes from the whole matrix (bin/phyloselect.py:381-398), with
+        the repulsive force summed exactly on the GPU.  y0 (float32 [n, 2]) replaces the seeded start.  metric: the metric of
+        the lists (KT, a correlation, is refused).  numpy in -> numpy out (po_tsne); torch CUDA tensors in -> tensor out
+        (po_tsne_affinities_dev + po_tsne_dev), the same bytes.  want_stats: (y, stats) with kl, iterations, grad_norm,
+        history [(iteration, kl, grad_norm) of every check] and, for numpy input, affinities_ms / optimise_ms."""
+        n, k = idx.shape
+        code, f32 = _tsne_list_args(metric, val, perplexity)
+        if y0 is None:
+            y0 = tsne_start(n, seed)
+        if _is_torch(idx):
+            import torch
+            if not _is_torch(y0):
+                y0 = torch.from_numpy(np.ascontiguousarray(y0, dtype=np.float32)).to(idx.device)
+            a = self.tsne_affinities(idx, val, perplexity, metric)
+            return self.tsne_optimise(a["rowptr"], a["col"], a["p"], y0.contiguous(), max_iter, exploration_iter, want_stats)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float32 if f32 else np.float64)
+        y0 = np.ascontiguousarray(y0, dtype=np.float32)
+        if y0.shape != (n, 2):
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "y0 must have shape (%d, 2), got %r" % (n, y0.shape))
+        params, hist = _tsne_params(max_iter, exploration_iter)
+        res = PoTsneResult()
+        y = np.zeros((n, 2), dtype=np.float32)
+        check(self._lib.po_tsne(self._h, n, k, code, PO_F32 if f32 else PO_F64, _np_ptr(idx), _np_ptr(val), float(perplexity),
+                                _np_ptr(y0), ctypes.byref(params), _np_ptr(y), ctypes.byref(res)))
+        return (y, _tsne_stats(res, hist)) if want_stats else y
+
     def _pairwise(self, counts, totals, freq, metric, row_begin, row_end, dtype, symmetric, out, want_stats,
                   extra_flags=0):
         if metric not in METRICS:
@@ -403,6 +503,56 @@ class Context:
                          "pairs": stats.pairs, "tiles": stats.tiles, "kernel_id": stats.kernel_id,
                     "rc_folded": bool(stats.rc_folded)}
         return out
+
+
+def tsne_neighbours(n, perplexity):
+    """neighbours per point t-SNE reads at this perplexity: min(n - 1, int(3 * perplexity + 1)), scikit-learn's n_neighbors"""
+    return min(n - 1, int(3.0 * perplexity + 1))
+
+
+def check_tsne_perplexity(perplexity):
+    """perplexity of the t-SNE entry points: 1 <= p and int(3 p + 1) <= PO_KNN_MAX_K (PO_EINVAL otherwise)"""
+    try:
+        p = float(perplexity)
+    except (TypeError, ValueError):
+        p = float("nan")
+    if not p >= 1.0 or int(3.0 * p + 1) > PO_KNN_MAX_K:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "perplexity must satisfy 1 <= perplexity and int(3 * perplexity + 1) <= %d, "
+                                  "i.e. at most %d (got %r)" % (PO_KNN_MAX_K, (PO_KNN_MAX_K - 1) // 3, perplexity))
+    return p
+
+
+def tsne_start(n, seed=0):
+    """scikit-learn's init="random": 1e-4 * RandomState(seed).standard_normal((n, 2)) as float32"""
+    return (1e-4 * np.random.RandomState(seed).standard_normal(size=(n, 2))).astype(np.float32)
+
+
+def _tsne_list_args(metric, val, perplexity):
+    if metric not in METRICS:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "unknown metric %r" % (metric,))
+    check_tsne_perplexity(perplexity)
+    return METRICS[metric], str(val.dtype) in ("float32", "torch.float32")
+
+
+def _tsne_params(max_iter, exploration_iter):
+    params = PoTsneParams()
+    params.max_iter = int(max_iter)
+    params.exploration_iter = 0 if exploration_iter is None else int(exploration_iter)
+    if int(max_iter) < 1 or params.exploration_iter < 0:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "max_iter must be at least 1 (got %r)" % (max_iter,))
+    cap = int(max_iter) // 50 + 2
+    hist = (ctypes.c_double * (3 * cap))()
+    params.history = ctypes.cast(hist, ctypes.POINTER(ctypes.c_double))
+    params.history_cap = cap
+    return params, hist
+
+
+def _tsne_stats(res, hist):
+    m = min(res.history_len, len(hist) // 3)
+    return {"kl": res.kl, "iterations": res.iterations, "grad_norm": res.grad_norm, "z": res.z,
+            "history": [(int(hist[3 * i]), hist[3 * i + 1], hist[3 * i + 2]) for i in range(m)],
+            "affinities_ms": res.affinities_ms, "optimise_ms": res.optimise_ms, "repulsion_ms": res.repulsion_ms,
+            "attraction_ms": res.attraction_ms, "rest_ms": res.rest_ms}
 
 
 def check_knn_k(k):

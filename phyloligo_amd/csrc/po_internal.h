@@ -76,6 +76,10 @@ struct po_ctx {
     po_buf ws_tilelist;                // per-class tile lists of the int8 Gram path (po_gram_i8.hip)
     po_buf ws_fix;                     // po_fix_list of the JSD path (po_jsd_exact.hip)
     po_buf ws_knn;                     // panel slab + mirror of the k-NN drivers (po_knn*): grown once per call shape
+    po_buf ws_tsne_aff;                // t-SNE affinities: conditional probabilities and the temporary rows of the CSR (po_tsne.hip)
+    po_buf ws_tsne;                    // t-SNE gradient / optimiser: partial sums, two embeddings, update, gains
+    po_buf ws_tsne_csr;                // po_tsne (host pointers): lists, CSR and embeddings on the device
+    double* h_tsne = nullptr;          // pinned: 8 doubles read back by the t-SNE entry points
     void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of the host-pointer entry points (device -> host rows)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
@@ -280,5 +284,18 @@ struct po_knn_batch {
 size_t po_knn_select_shmem(uint32_t k, int val_f32);
 // desc: Kendall's tau (descending order); val_f32: the lists and candidates are float32 (else float64)
 int po_launch_knn_select(po_ctx* ctx, int32_t* d_idx, void* d_val, uint32_t k, int val_f32, int desc, const po_knn_batch& b);
+
+// t-SNE (po_tsne.hip)
+size_t po_tsne_affinity_workspace(uint64_t n, uint32_t k);
+int po_launch_tsne_affinities(po_ctx* ctx, uint64_t n, uint32_t k, int val_f32, const int32_t* d_idx, const void* d_val, double perplexity,
+                              double* d_beta, double* d_cond, void* ws, uint32_t* h_err);
+int po_launch_tsne_joint(po_ctx* ctx, uint64_t n, uint32_t k, const int32_t* d_idx, void* ws, int64_t* d_rowptr, int32_t* d_col, float* d_p,
+                         int step, int64_t* h_nnz, uint32_t* h_dup);
+size_t po_tsne_grad_workspace(uint64_t n);
+int po_launch_tsne_check_csr(po_ctx* ctx, const int64_t* d_rowptr, const int32_t* d_col, uint64_t n, uint64_t nnz, uint32_t* d_err);
+int po_launch_tsne_gradient(po_ctx* ctx, const int64_t* d_rowptr, const int32_t* d_col, const float* d_p, const float* d_y, uint64_t n,
+                            double exaggeration, void* ws, bool update, float* d_grad, float* d_y_out, float* d_upd, float* d_gains,
+                            double momentum, double lr, double min_gain, bool want_kl, bool want_gn, double** d_scalars,
+                            hipEvent_t* ev);   // ev (may be NULL): 4 events recorded before / after the repulsion, after Z, after the attraction
 
 static inline uint64_t po_round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }

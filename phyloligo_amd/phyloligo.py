@@ -395,6 +395,14 @@ def get_cmd(argv=None):
                         help="not in the reference: write the K nearest neighbours of every contig (1 <= K <= 1024) to -o as a "
                              "sparse CSR graph (scipy.sparse.load_npz reads it; row i: i itself, then its neighbours by distance) "
                              "instead of the N x N matrix; float64 values")
+    parser.add_argument("--tsne", action="store", dest="tsne", type=float, default=None, metavar="PERPLEXITY",
+                        help="not in the reference's phyloligo.py: embed the contigs in 2-D with t-SNE at this perplexity, from the "
+                             "int(3 * PERPLEXITY + 1) nearest neighbours of every contig, and write the n x 2 coordinates to -o as "
+                             "text (what phyloselect.py -t -p PERPLEXITY computes from the whole matrix); 1 <= PERPLEXITY <= 341")
+    parser.add_argument("--tsne-seed", action="store", dest="tsne_seed", type=int, default=0,
+                        help="with --tsne: seed of the random start, phyloselect.py's random_state [default:%(default)d]")
+    parser.add_argument("--tsne-iter", action="store", dest="tsne_iter", type=int, default=1000,
+                        help="with --tsne: most iterations of the optimiser, scikit-learn's max_iter [default:%(default)d]")
     params = parser.parse_args(argv)
     params.workdir = os.path.abspath(params.workdir)
     return params
@@ -410,6 +418,28 @@ def _knn_refused(params):
         return "Error, --knn writes a neighbour graph, not a matrix container: it cannot be combined with --large %s" % params.large
     if params.mthdrun not in ("joblib", "hip"):
         return "Error, --knn supports --method joblib|hip"
+    return None
+
+
+def _tsne_refused(params):
+    """the reason --tsne cannot run with these options, or None"""
+    if getattr(params, "tsne", None) is None:
+        return None
+    if params.knn is not None:
+        return "Error, --tsne writes an embedding and --knn a neighbour graph to -o: give one of them"
+    if params.large != "None":
+        return "Error, --tsne writes n x 2 coordinates as text, not a matrix container: it cannot be combined with --large %s" % params.large
+    if params.dist == "KT":
+        return "Error, --tsne needs a distance: -d KT is a correlation (its neighbour lists are ordered descending)"
+    if not params.tsne >= 1.0 or int(3.0 * params.tsne + 1) > PO_KNN_MAX_K:
+        return ("Error, --tsne PERPLEXITY needs 1 <= PERPLEXITY and int(3 * PERPLEXITY + 1) <= %d neighbours, i.e. at most %d (got %g)"
+                % (PO_KNN_MAX_K, (PO_KNN_MAX_K - 1) // 3, params.tsne))
+    if params.tsne_iter < 1:
+        return "Error, --tsne-iter needs at least 1 iteration (got %d)" % params.tsne_iter
+    if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "Error, --tsne runs on one GPU: an embedding over several ranks (--gpus N > 1) is out of scope"
+    if params.mthdrun not in ("joblib", "hip"):
+        return "Error, --tsne supports --method joblib|hip"
     return None
 
 
@@ -445,10 +475,11 @@ def main_distributed(params):
             sys.exit(1)
     if params.strand not in STRANDS or params.dist not in METRICS:
         sys.exit(1)
-    if _knn_refused(params):
-        if rank == 0:
-            print(_knn_refused(params), file=sys.stderr)
-        sys.exit(1)
+    for refused in (_tsne_refused(params), _knn_refused(params)):
+        if refused:
+            if rank == 0:
+                print(refused, file=sys.stderr)
+            sys.exit(1)
     from .dist import first_contact
     first_contact("cuda.set_device", torch.cuda.set_device, local)
     if rehearsal:
@@ -621,9 +652,10 @@ def main(argv=None):
         params.pattern = str("1") * params.pattern
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return main_distributed(params)
-    if _knn_refused(params):
-        print(_knn_refused(params), file=sys.stderr)
-        sys.exit(1)
+    for refused in (_tsne_refused(params), _knn_refused(params)):
+        if refused:
+            print(refused, file=sys.stderr)
+            sys.exit(1)
     t_start = time.perf_counter()
     print("Using pattern {}".format(params.pattern))
     if not os.path.isdir(params.workdir):
@@ -637,6 +669,8 @@ def main(argv=None):
     t_freq = time.perf_counter()
     print("Computing Pairwise distances")
     t_dist0 = time.perf_counter()
+    if params.tsne is not None:
+        return _tsne_single(params, frequencies, t_start, t_freq, t_dist0)
     if params.knn is not None:
         return _knn_single(params, frequencies, t_start, t_freq, t_dist0)
     res = compute_distances(params.mthdrun, params.large, frequencies, freq_name, params.out_file, params.dist,
@@ -679,6 +713,41 @@ def _knn_single(params, frequencies, t_start, t_freq, t_dist0):
     return 0
 
 
+LAST_TSNE = None         # tsne_ms / tsne_iterations / tsne_kl of the last --tsne run (what --json-stats reports)
+
+
+def _tsne_single(params, frequencies, t_start, t_freq, t_dist0):
+    """--tsne: the graph as --knn int(3 p + 1) selects it (po_knn, float64), embedded by po_tsne, written to -o as text"""
+    global LAST_STAGE2, LAST_TSNE
+    if frequencies is None:
+        return 0
+    counts, totals = frequencies.counts, frequencies.totals
+    n = frequencies.shape[0]
+    if n < 4:
+        print("Error, --tsne needs at least 4 contigs (got %d)" % n, file=sys.stderr)
+        sys.exit(1)
+    ctx = _context()
+    idx, val, st = ctx.knn(counts, totals, api.tsne_neighbours(n, params.tsne), params.dist, "float64", want_stats=True)
+    LAST_STAGE2 = dict(st, rows=[0, n])
+    t0 = time.perf_counter()
+    try:
+        y, ts = ctx.tsne(idx, val, params.tsne, seed=params.tsne_seed, max_iter=params.tsne_iter, want_stats=True, metric=params.dist)
+    except api._lib.PhyloligoError as e:
+        print("Error, --tsne: %s" % e, file=sys.stderr)
+        sys.exit(1)
+    t_dist = time.perf_counter()
+    LAST_TSNE = {"tsne_ms": (t_dist - t0) * 1e3, "tsne_iterations": ts["iterations"], "tsne_kl": ts["kl"]}
+    _timing("single process: k-NN graph + t-SNE %.3f s" % (t_dist - t_dist0))
+    if params.out_freq_file:
+        print("Writing frequency matrix")
+        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
+    print("Writing t-SNE embedding")
+    np.savetxt(params.out_file, y)
+    if params.json_stats:
+        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
+    return 0
+
+
 class _Shape:
     """stands in for the frequency matrix where only its shape is wanted (--json-stats of a multi-rank run)"""
 
@@ -699,6 +768,7 @@ def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpu
              "stage2_first_call": LAST_STAGE2,
              **({} if getattr(params, "knn", None) is None else
                 {"knn": params.knn, "knn_select_ms": None if LAST_STAGE2 is None else LAST_STAGE2.get("select_ms")}),
+             **({} if getattr(params, "tsne", None) is None or LAST_TSNE is None else dict(LAST_TSNE, tsne_perplexity=params.tsne)),
              "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
     with open(params.json_stats, "w") as fh:
         json.dump(stats, fh, indent=1)
