@@ -315,6 +315,51 @@ int po_tsne_dev(po_ctx* ctx, uint64_t n, const int64_t* d_rowptr, const int32_t*
 int po_tsne(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* idx, const void* val, double perplexity,
             const float* y0, const po_tsne_params* params, float* y, po_tsne_result* result);
 
+/* ---- k-medoids on the distance matrix: the clusters phyloselect.py writes out ------------------------------------------------ *
+ * Replaces the KMedoids class the reference ships (bin/phyloselect.py:37-309) as phyloselect.py calls it:
+ * KMedoids(n_clusters, distance_metric="precomputed").fit(matrix) on the whole matrix (:578-595, :647).  Decision for decision:
+ *   start    init_medoids == NULL: init="heuristic" (_get_initial_medoid_indices, :298-302) - the n_clusters rows with the smallest
+ *            row sums, ascending, ties to the smaller row.  Else n_clusters distinct rows, a HOST array in both forms (init="random",
+ *            :293-296, is RandomState(seed).permutation(n)[:n_clusters] computed by the caller).
+ *   assign   label[j] = argmin_c matrix[medoid[c]][j], the smaller c wins a tie (_get_cluster_ics, :190-198)
+ *   update   per cluster, against those labels: the member with the smallest sum over the members (ties: the smaller row) replaces
+ *            the medoid if that sum is strictly below the medoid's own; an empty cluster keeps its medoid
+ *            (_update_medoid_ics_in_place, :200-240)
+ *   loop     until no medoid changed or max_iter passes ran (fit, :143-168; the reference's default is 300).  labels are those of
+ *            the LAST assignment: when max_iter ends the loop they do not reflect the last update, as in the reference.
+ * matrix: [n][n] float32 / float64 (dtype), row major, leading dimension ld >= n elements; read by rows, never written.  Every sum
+ * accumulates in float64 whatever dtype is, and a row's sum depends on the row, the labels and n alone (fixed order, no
+ * floating-point atomics): the same input gives the same bytes.  Rows on 16-byte boundaries (pointer and ld) are read with 16-byte
+ * loads, any other layout element by element with the same result.  The host reads back one flag word per iteration; with the
+ * heuristic start also the n row sums, once.  PO_EINVAL: n_clusters < 1 or > n, max_iter < 1, ld < n, an init row outside 0..n-1
+ * or given twice, and - heuristic start only - a row whose sum is NaN (Bray-Curtis gives 0/0 for two empty records); the message
+ * names the first such row.  With init_medoids the result for a matrix that holds NaN is unspecified (a NaN never wins the
+ * assignment, and sorts after every number in the update).
+ *   d_labels int32 [n], d_medoids int32 [n_clusters]     result (may be NULL; asking for it adds one small kernel and device events) */
+typedef struct po_kmedoids_result {
+    uint32_t iterations;       /* assignment passes made (the reference's n_iter_) */
+    uint32_t converged;        /* 1: the last update changed no medoid; 0: max_iter ended the loop */
+    uint32_t empty_clusters;   /* clusters without a member in the returned labels */
+    uint32_t reserved;
+    double inertia;            /* sum over j of matrix[medoid[label[j]]][j] for the returned labels and medoids */
+    double start_ms;           /* HIP-event times: the start (row sums + selection on the host) ... */
+    double rowsum_ms, assign_ms, update_ms;   /* ... and, summed over the iterations, the three steps of an iteration */
+} po_kmedoids_result;
+int po_kmedoids_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, uint32_t n_clusters,
+                    const int32_t* init_medoids, uint32_t max_iter, int32_t* d_labels, int32_t* d_medoids, po_kmedoids_result* result);
+/* Host pointers: the matrix is copied to the device (PO_ENOMEM, with the size in the message, when it does not fit). */
+int po_kmedoids(po_ctx* ctx, const void* matrix, int dtype, uint64_t n, uint64_t ld, uint32_t n_clusters, const int32_t* init_medoids,
+                uint32_t max_iter, int32_t* labels, int32_t* medoids, po_kmedoids_result* result);
+/* The two pieces the loop is made of.  Costs: d_costs[t] = sum over j with d_labels[j] == d_labels[r] of matrix[r][j], float64, for
+ * r = d_rows[t], t < n_rows - or for every row r = t < n when d_rows is NULL (n_rows 0 or n): numpy.sum(D_in, axis=1) of :218-223 for
+ * all clusters at once.  The bytes of a row's cost do not depend on which other rows are asked for.  Labels are any int32.
+ * Assign: d_labels [n] for the medoids d_medoids [n_clusters] (device; rows of the matrix, checked: PO_EINVAL names the first
+ * outside 0..n-1).  Both synchronise the stream once when they check a device index list.                                     */
+int po_kmedoids_costs_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, const int32_t* d_labels,
+                          const int32_t* d_rows, uint64_t n_rows, double* d_costs);
+int po_kmedoids_assign_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, uint32_t n_clusters,
+                           const int32_t* d_medoids, int32_t* d_labels);
+
 /* bytes of device workspace po_pairwise_dev will hold for this problem (allocated lazily on
  * first use and kept by the context; call once before timing to keep hipMalloc out of it)    */
 int po_pairwise_reserve(po_ctx* ctx, uint64_t n, uint32_t dim, int metric);

@@ -22,6 +22,10 @@ if _n > 1 and any(a == "--tsne" or a.startswith("--tsne=") for a in sys.argv[1:]
     # refused before any rank is started (phyloligo._tsne_refused says the same inside a rank)
     sys.stderr.write("Error, --tsne runs on one GPU: an embedding over several ranks (--gpus N > 1) is out of scope\n")
     sys.exit(1)
+_kmedoids = any(a == "--kmedoids" or a.startswith("--kmedoids=") for a in sys.argv[1:])
+if _n > 1 and _kmedoids:
+    sys.stderr.write("Error, --kmedoids runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope\n")
+    sys.exit(1)
 if launch.needs_launcher(_n):
     # --gpus N > 1: this process only starts one rank per GPU (python -m torch.distributed.run ... -m phyloligo_amd <same
     # arguments>) and waits for them - the reference fans out to its own workers the same way (bin/phyloligo.py:386-390).
@@ -30,7 +34,7 @@ if launch.needs_launcher(_n):
     sys.exit(launch.spawn_ranks(_n, ["-m", "phyloligo_amd"], sys.argv[1:],
                                 timeout_s=float(os.environ.get("PO_CLI_LAUNCH_TIMEOUT", "0")) or None))
 
-if int(os.environ.get("WORLD_SIZE", "1")) <= 1:
+if int(os.environ.get("WORLD_SIZE", "1")) <= 1 and not _kmedoids:      # (--kmedoids keeps the matrix in a torch CUDA tensor)
     _lib.PREFER_NO_TORCH = True      # one process, one GPU: numpy + the host-pointer entry points of the C ABI are enough
 
 from .phyloligo import main  # noqa: E402

@@ -63,6 +63,12 @@ class PoTsneResult(ctypes.Structure):
                 ("repulsion_ms", ctypes.c_double), ("attraction_ms", ctypes.c_double), ("rest_ms", ctypes.c_double)]
 
 
+class PoKmedoidsResult(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("empty_clusters", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("inertia", ctypes.c_double), ("start_ms", ctypes.c_double),
+                ("rowsum_ms", ctypes.c_double), ("assign_ms", ctypes.c_double), ("update_ms", ctypes.c_double)]
+
+
 class PhyloligoError(RuntimeError):
     def __init__(self, status, message):
         super().__init__("phyloligo_amd: %s (status %d)" % (message, status))
@@ -111,6 +117,10 @@ SIGNATURES = {
     "po_tsne_gradient_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _dbl, _vp, _c.POINTER(_dbl), _c.POINTER(_dbl)]),
     "po_tsne_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _c.POINTER(PoTsneParams), _vp, _c.POINTER(PoTsneResult)]),
     "po_tsne": (_int, [_vp, _u64, _u32, _int, _int, _vp, _vp, _dbl, _vp, _c.POINTER(PoTsneParams), _vp, _c.POINTER(PoTsneResult)]),
+    "po_kmedoids_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _c.POINTER(PoKmedoidsResult)]),
+    "po_kmedoids": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _c.POINTER(PoKmedoidsResult)]),
+    "po_kmedoids_costs_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _vp, _u64, _vp]),
+    "po_kmedoids_assign_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _vp]),
     "po_fasta_scan": (_int, [_vp, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),
     "po_fasta_extract": (_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
     "po_file_read": (_int, [_cp, _vp, _u64]),

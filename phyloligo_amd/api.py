@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoStats, PoTsneParams, PoTsneResult,
+from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoKmedoidsResult, PoStats, PoTsneParams, PoTsneResult,
                    check)
 
 
@@ -442,6 +442,125 @@ class Context:
         check(self._lib.po_tsne(self._h, n, k, code, PO_F32 if f32 else PO_F64, _np_ptr(idx), _np_ptr(val), float(perplexity),
                                 _np_ptr(y0), ctypes.byref(params), _np_ptr(y), ctypes.byref(res)))
         return (y, _tsne_stats(res, hist)) if want_stats else y
+
+    # ---- k-medoids on a distance matrix --------------------------------------------------------
+    def _kmed_matrix(self, matrix):
+        """(is_torch, matrix, dtype code, n, ld) of a 2-D float32 / float64 matrix with unit inner stride and row stride >= n"""
+        if _is_torch(matrix):
+            import torch
+            self._check_device(matrix)
+            if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1] or matrix.dtype not in (torch.float32, torch.float64):
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must be a square float32 / float64 tensor (got %s %s)"
+                                          % (tuple(matrix.shape), matrix.dtype))
+            n = matrix.shape[0]
+            if n > 1 and matrix.stride(1) != 1:
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must have unit inner stride (strides %r)" % (tuple(matrix.stride()),))
+            ld = matrix.stride(0) if n > 1 else max(n, 1)
+            return True, matrix, PO_F32 if matrix.dtype == torch.float32 else PO_F64, n, ld
+        if not isinstance(matrix, np.ndarray) or matrix.dtype not in (np.float32, np.float64):
+            matrix = np.asarray(matrix, dtype=np.float64)
+        if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1]:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must be square (got shape %r)" % (matrix.shape,))
+        n = matrix.shape[0]
+        if n > 1 and (matrix.strides[1] != matrix.itemsize or matrix.strides[0] % matrix.itemsize or matrix.strides[0] < 0):
+            matrix = np.ascontiguousarray(matrix)
+        ld = matrix.strides[0] // matrix.itemsize if n > 1 else max(n, 1)
+        return False, matrix, PO_F32 if matrix.dtype == np.float32 else PO_F64, n, ld
+
+    def kmedoids(self, matrix, n_clusters=8, max_iter=300, init="heuristic", want_stats=False):
+        """k-medoids of a precomputed distance matrix [n, n] (float32 / float64, unit inner stride, any row stride >= n): what
+        the reference's KMedoids(n_clusters, distance_metric="precomputed", max_iter=max_iter).fit(matrix) decides
+        (bin/phyloselect.py:37-309), on the GPU with float64 sums.  init: "heuristic" (the rows with the smallest sums) or
+        n_clusters distinct row indices - RandomState(seed).permutation(n)[:n_clusters] is the reference's init="random".
+        Returns (labels int32 [n], medoids int32 [n_clusters]); with want_stats also a dict (iterations, converged, inertia,
+        empty_clusters, start_ms / rowsum_ms / assign_ms / update_ms).  numpy in -> numpy out (po_kmedoids: the matrix is
+        copied to the device); torch CUDA tensor in -> tensors out on torch's current stream (po_kmedoids_dev).  With the
+        heuristic start a row that sums to NaN is refused (PO_EINVAL); with explicit rows a NaN gives an unspecified result."""
+        is_t, matrix, code, n, ld = self._kmed_matrix(matrix)
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= n:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "n_clusters must be an integer in 1..n = %d (got %r)" % (n, n_clusters))
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "max_iter must be at least 1 (got %r)" % (max_iter,))
+        k = int(n_clusters)
+        start = None
+        if not (isinstance(init, str) and init == "heuristic"):
+            if isinstance(init, str):
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "init must be \"heuristic\" or %d row indices (got %r)" % (k, init))
+            start = init.cpu().numpy() if _is_torch(init) else np.asarray(init)
+            if start.shape != (k,) or start.dtype.kind not in "iu" or (start.size and (start.min() < 0 or start.max() >= n)):
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "init must be %d integer row indices in 0..%d (got %r)" % (k, n - 1, init))
+            start = np.ascontiguousarray(start, dtype=np.int32)
+        sp = _np_ptr(start) if start is not None else None
+        res = PoKmedoidsResult()
+        rp = ctypes.byref(res) if want_stats else None
+        if is_t:
+            import torch
+            labels = torch.empty((n,), dtype=torch.int32, device=matrix.device)
+            medoids = torch.empty((k,), dtype=torch.int32, device=matrix.device)
+            self._use_torch_stream()
+            check(self._lib.po_kmedoids_dev(self._h, matrix.data_ptr(), code, n, ld, k, sp, int(max_iter), labels.data_ptr(),
+                                            medoids.data_ptr(), rp))
+        else:
+            labels = np.zeros(n, dtype=np.int32)
+            medoids = np.zeros(k, dtype=np.int32)
+            check(self._lib.po_kmedoids(self._h, _np_ptr(matrix), code, n, ld, k, sp, int(max_iter), _np_ptr(labels), _np_ptr(medoids), rp))
+        if want_stats:
+            return labels, medoids, {"iterations": res.iterations, "converged": bool(res.converged), "inertia": res.inertia,
+                                     "empty_clusters": res.empty_clusters, "start_ms": res.start_ms, "rowsum_ms": res.rowsum_ms,
+                                     "assign_ms": res.assign_ms, "update_ms": res.update_ms}
+        return labels, medoids
+
+    def _kmed_device(self, matrix):
+        import torch
+        is_t, matrix, code, n, ld = self._kmed_matrix(matrix)
+        if not is_t:
+            matrix = torch.from_numpy(matrix).cuda(self.device)      # a strided view arrives with its row stride
+            ld = matrix.stride(0) if n > 1 else max(n, 1)
+        return is_t, matrix, code, n, ld
+
+    def kmedoids_costs(self, matrix, labels, rows=None):
+        """float64 [n]: for every row i the sum of matrix[i, j] over the columns j with labels[j] == labels[i] - the candidate
+        costs of one k-medoids update (po_kmedoids_costs_dev).  rows: only these rows, in this order; the bytes of a row's cost
+        are the same either way.  numpy in -> numpy out; torch CUDA tensors in -> tensor out."""
+        import torch
+        is_t, matrix, code, n, ld = self._kmed_device(matrix)
+        dev = matrix.device
+        labels = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+        self._check_device(labels)
+        if labels.dtype != torch.int32 or labels.shape != (n,):
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels must be int32 [%d] (got %s %s)" % (n, labels.dtype, tuple(labels.shape)))
+        labels = labels.contiguous()
+        d_rows, count = None, n
+        if rows is not None:
+            d_rows = rows if _is_torch(rows) else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
+            self._check_device(d_rows)
+            if d_rows.dtype != torch.int32 or d_rows.dim() != 1:
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "rows must be a 1-D int32 index list")
+            d_rows = d_rows.contiguous()
+            count = d_rows.numel()
+        out = torch.empty((count,), dtype=torch.float64, device=dev)
+        self._use_torch_stream()
+        check(self._lib.po_kmedoids_costs_dev(self._h, matrix.data_ptr(), code, n, ld, labels.data_ptr(),
+                                              d_rows.data_ptr() if d_rows is not None else None, count if d_rows is not None else 0,
+                                              out.data_ptr()))
+        return out if is_t else out.cpu().numpy()
+
+    def kmedoids_assign(self, matrix, medoids):
+        """int32 [n]: labels[j] = argmin over c of matrix[medoids[c], j], the smaller c wins a tie (po_kmedoids_assign_dev).
+        numpy in -> numpy out; torch CUDA tensors in -> tensor out."""
+        import torch
+        is_t, matrix, code, n, ld = self._kmed_device(matrix)
+        dev = matrix.device
+        medoids = medoids if _is_torch(medoids) else torch.from_numpy(np.ascontiguousarray(medoids, dtype=np.int32)).to(dev)
+        self._check_device(medoids)
+        if medoids.dtype != torch.int32 or medoids.dim() != 1:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "medoids must be a 1-D int32 index list")
+        medoids = medoids.contiguous()
+        labels = torch.empty((n,), dtype=torch.int32, device=dev)
+        self._use_torch_stream()
+        check(self._lib.po_kmedoids_assign_dev(self._h, matrix.data_ptr(), code, n, ld, medoids.numel(), medoids.data_ptr(),
+                                               labels.data_ptr()))
+        return labels if is_t else labels.cpu().numpy()
 
     def _pairwise(self, counts, totals, freq, metric, row_begin, row_end, dtype, symmetric, out, want_stats,
                   extra_flags=0):

@@ -80,6 +80,8 @@ struct po_ctx {
     po_buf ws_tsne;                    // t-SNE gradient / optimiser: partial sums, two embeddings, update, gains
     po_buf ws_tsne_csr;                // po_tsne (host pointers): lists, CSR and embeddings on the device
     double* h_tsne = nullptr;          // pinned: 8 doubles read back by the t-SNE entry points
+    po_buf ws_kmed;                    // k-medoids: pair list (rows / medoids, labels / clusters), costs, per-cluster minima (po_kmedoids.hip)
+    double* h_kmed = nullptr;          // pinned: 8 doubles read back by the k-medoids entry points
     void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of the host-pointer entry points (device -> host rows)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };

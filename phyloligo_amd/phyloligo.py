@@ -403,6 +403,15 @@ def get_cmd(argv=None):
                         help="with --tsne: seed of the random start, phyloselect.py's random_state [default:%(default)d]")
     parser.add_argument("--tsne-iter", action="store", dest="tsne_iter", type=int, default=1000,
                         help="with --tsne: most iterations of the optimiser, scikit-learn's max_iter [default:%(default)d]")
+    parser.add_argument("--kmedoids", action="store", dest="kmedoids", type=int, default=None, metavar="K",
+                        help="not in the reference's phyloligo.py: cluster the contigs into K groups with k-medoids on the N x N "
+                             "matrix, which stays in GPU memory, and write one cluster label per contig to -o, in input order "
+                             "(what phyloselect.py -m kmedoids computes from the matrix file); 1 <= K <= N")
+    parser.add_argument("--kmedoids-iter", action="store", dest="kmedoids_iter", type=int, default=300,
+                        help="with --kmedoids: most iterations, the reference's max_iter [default:%(default)d]")
+    parser.add_argument("--kmedoids-dtype", action="store", dest="kmedoids_dtype", choices=["float64", "float32"], default="float64",
+                        help="with --kmedoids: element type of the matrix in GPU memory; float32 takes half the memory, sums are "
+                             "float64 either way [default:%(default)s]")
     params = parser.parse_args(argv)
     params.workdir = os.path.abspath(params.workdir)
     return params
@@ -443,6 +452,27 @@ def _tsne_refused(params):
     return None
 
 
+def _kmedoids_refused(params):
+    """the reason --kmedoids cannot run with these options, or None"""
+    if getattr(params, "kmedoids", None) is None:
+        return None
+    if params.knn is not None or getattr(params, "tsne", None) is not None:
+        return ("Error, --kmedoids writes cluster labels to -o, --knn a neighbour graph and --tsne an embedding: give one of them")
+    if params.large != "None":
+        return "Error, --kmedoids writes one label per contig as text, not a matrix container: it cannot be combined with --large %s" % params.large
+    if params.dist == "KT":
+        return "Error, --kmedoids needs a distance: -d KT is a correlation (larger means closer)"
+    if params.kmedoids < 1:
+        return "Error, --kmedoids K needs 1 <= K <= number of contigs (got %d)" % params.kmedoids
+    if params.kmedoids_iter < 1:
+        return "Error, --kmedoids-iter needs at least 1 iteration (got %d)" % params.kmedoids_iter
+    if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "Error, --kmedoids runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope"
+    if params.mthdrun not in ("joblib", "hip"):
+        return "Error, --kmedoids supports --method joblib|hip"
+    return None
+
+
 def _write_knn(params, counts, idx, val):
     api.write_knn_npz(params.out_file, idx, val, api.knn_self_values(params.dist, val, counts=counts))
 
@@ -475,7 +505,7 @@ def main_distributed(params):
             sys.exit(1)
     if params.strand not in STRANDS or params.dist not in METRICS:
         sys.exit(1)
-    for refused in (_tsne_refused(params), _knn_refused(params)):
+    for refused in (_kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
         if refused:
             if rank == 0:
                 print(refused, file=sys.stderr)
@@ -652,7 +682,7 @@ def main(argv=None):
         params.pattern = str("1") * params.pattern
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return main_distributed(params)
-    for refused in (_tsne_refused(params), _knn_refused(params)):
+    for refused in (_kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
         if refused:
             print(refused, file=sys.stderr)
             sys.exit(1)
@@ -669,6 +699,8 @@ def main(argv=None):
     t_freq = time.perf_counter()
     print("Computing Pairwise distances")
     t_dist0 = time.perf_counter()
+    if params.kmedoids is not None:
+        return _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0)
     if params.tsne is not None:
         return _tsne_single(params, frequencies, t_start, t_freq, t_dist0)
     if params.knn is not None:
@@ -748,6 +780,67 @@ def _tsne_single(params, frequencies, t_start, t_freq, t_dist0):
     return 0
 
 
+LAST_KMEDOIDS = None     # what --json-stats reports of the last --kmedoids run
+
+
+def write_labels(path, labels):
+    """one integer cluster label per contig, in input order: n lines, each an integer and a line feed"""
+    with open(path, "w") as fh:
+        fh.write("".join("%d\n" % int(x) for x in labels))
+
+
+def _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0):
+    """--kmedoids: the dense matrix computed into device memory (po_pairwise_dev), clustered there (po_kmedoids_dev); only the
+    labels come back"""
+    global LAST_STAGE2, LAST_KMEDOIDS
+    if frequencies is None:
+        return 0
+    import torch
+    n = frequencies.shape[0]
+    k = params.kmedoids
+    if not 1 <= k <= n:
+        print("Error, --kmedoids K needs 1 <= K <= number of contigs (got K = %d for %d contigs)" % (k, n), file=sys.stderr)
+        sys.exit(1)
+    ctx = _context()
+    dev = torch.device("cuda", ctx.device)
+    f32 = params.kmedoids_dtype == "float32"
+    esz = 4 if f32 else 8
+    ld = (n + 128 // esz - 1) // (128 // esz) * (128 // esz)            # rows on whole 128-byte lines
+    try:
+        buf = torch.empty((n, ld), dtype=torch.float32 if f32 else torch.float64, device=dev)
+    except torch.cuda.OutOfMemoryError:
+        print("Error, --kmedoids: the %d x %d %s matrix (%.1f GB) does not fit the memory of the GPU%s"
+              % (n, n, params.kmedoids_dtype, n * ld * esz / 1e9,
+                 "" if f32 else "; --kmedoids-dtype float32 takes half (%.1f GB)" % (n * ld * 4 / 1e9)), file=sys.stderr)
+        sys.exit(1)
+    d_counts = torch.from_numpy(np.ascontiguousarray(frequencies.counts).view(np.int32)).to(dev)
+    d_totals = torch.from_numpy(np.ascontiguousarray(frequencies.totals).view(np.int64)).to(dev)
+    _, st = ctx.pairwise(d_counts, d_totals, params.dist, dtype=params.kmedoids_dtype, out=buf, want_stats=True)
+    LAST_STAGE2 = dict(st, rows=[0, n])
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    try:
+        labels, medoids, ks = ctx.kmedoids(buf[:, :n], k, max_iter=params.kmedoids_iter, want_stats=True)
+    except api._lib.PhyloligoError as e:
+        print("Error, --kmedoids: %s" % e, file=sys.stderr)
+        sys.exit(1)
+    labels, medoids = labels.cpu().numpy(), medoids.cpu().numpy()
+    t_dist = time.perf_counter()
+    LAST_KMEDOIDS = {"kmedoids": k, "kmedoids_medoids": [int(x) for x in medoids], "kmedoids_iterations": ks["iterations"],
+                     "kmedoids_converged": ks["converged"], "kmedoids_sizes": [int(x) for x in np.bincount(labels, minlength=k)],
+                     "kmedoids_ms": (t_dist - t0) * 1e3, "kmedoids_inertia": ks["inertia"], "kmedoids_dtype": params.kmedoids_dtype,
+                     "kmedoids_phases_ms": {p: ks[p + "_ms"] for p in ("start", "rowsum", "assign", "update")}}
+    _timing("single process: matrix + k-medoids %.3f s" % (t_dist - t_dist0))
+    if params.out_freq_file:
+        print("Writing frequency matrix")
+        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
+    print("Writing cluster labels")
+    write_labels(params.out_file, labels)
+    if params.json_stats:
+        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
+    return 0
+
+
 class _Shape:
     """stands in for the frequency matrix where only its shape is wanted (--json-stats of a multi-rank run)"""
 
@@ -769,6 +862,7 @@ def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpu
              **({} if getattr(params, "knn", None) is None else
                 {"knn": params.knn, "knn_select_ms": None if LAST_STAGE2 is None else LAST_STAGE2.get("select_ms")}),
              **({} if getattr(params, "tsne", None) is None or LAST_TSNE is None else dict(LAST_TSNE, tsne_perplexity=params.tsne)),
+             **({} if getattr(params, "kmedoids", None) is None or LAST_KMEDOIDS is None else LAST_KMEDOIDS),
              "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
     with open(params.json_stats, "w") as fh:
         json.dump(stats, fh, indent=1)
