@@ -360,6 +360,22 @@ int po_kmedoids_costs_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t
 int po_kmedoids_assign_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, uint32_t n_clusters,
                            const int32_t* d_medoids, int32_t* d_labels);
 
+/* ---- row medians of a matrix in HBM ---------------------------------------------------------- *
+ * d_out[i] = median of row i of d_matrix [rows][n] (float32 / float64, row major, leading dimension ld >= n elements; read,
+ * never written), over all n columns - the diagonal of a distance matrix included: R's apply(dist_matrix, 1, median), the first
+ * step of the reference's outlier clip (bin/phyloselect.R:339-357).  The values are widened to float64 and ordered as numbers
+ * (-0 = +0); lo is the value at rank (n-1)/2, hi the value at rank n/2 (0-based); the median is lo for odd n and (lo + hi) * 0.5
+ * for even n: numpy.median(m.astype(float64), axis=1).  A row that holds a NaN gives NaN; +-inf are ordinary values.  The result
+ * is exact (an element of the row or the mean of two), so it depends on nothing but the row: not on ld, the alignment (rows on
+ * 16-byte boundaries are read with 16-byte loads, any other layout element by element) or the launch.  Works on the context's
+ * stream without synchronising it.  rows == 0 or n == 0: nothing is done.  PO_EINVAL: n > 2^31 - 1, ld < n, a dtype other than
+ * PO_F32 / PO_F64.
+ * po_row_medians_passes: how many times the last po_row_medians_dev call of this context read a row from memory, summed over
+ * its rows (the selection re-reads a row once per radix digit it needs; passes / rows is the bytes read per matrix byte).
+ * Synchronises the stream.                                                                                                  */
+int po_row_medians_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t rows, uint64_t n, uint64_t ld, double* d_out);
+int po_row_medians_passes(po_ctx* ctx, uint64_t* passes);
+
 /* bytes of device workspace po_pairwise_dev will hold for this problem (allocated lazily on
  * first use and kept by the context; call once before timing to keep hipMalloc out of it)    */
 int po_pairwise_reserve(po_ctx* ctx, uint64_t n, uint32_t dim, int metric);

@@ -26,6 +26,24 @@ _kmedoids = any(a == "--kmedoids" or a.startswith("--kmedoids=") for a in sys.ar
 if _n > 1 and _kmedoids:
     sys.stderr.write("Error, --kmedoids runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope\n")
     sys.exit(1)
+
+
+def _opt(argv, name, default):
+    for i, a in enumerate(argv):
+        if a == name and i + 1 < len(argv):
+            return argv[i + 1]
+        if a.startswith(name + "="):
+            return a.split("=", 1)[1]
+    return default
+
+
+try:
+    _clip = float(_opt(sys.argv[1:], "--clip-percentile", "1")) != 1 or int(_opt(sys.argv[1:], "--min-size", "0")) != 0
+except ValueError:
+    _clip = False                        # get_cmd() reports the malformed value
+if _n > 1 and _clip:
+    sys.stderr.write("Error, --clip-percentile / --min-size run on one GPU: a clip over several ranks (--gpus N > 1) is out of scope\n")
+    sys.exit(1)
 if launch.needs_launcher(_n):
     # --gpus N > 1: this process only starts one rank per GPU (python -m torch.distributed.run ... -m phyloligo_amd <same
     # arguments>) and waits for them - the reference fans out to its own workers the same way (bin/phyloligo.py:386-390).
@@ -34,7 +52,7 @@ if launch.needs_launcher(_n):
     sys.exit(launch.spawn_ranks(_n, ["-m", "phyloligo_amd"], sys.argv[1:],
                                 timeout_s=float(os.environ.get("PO_CLI_LAUNCH_TIMEOUT", "0")) or None))
 
-if int(os.environ.get("WORLD_SIZE", "1")) <= 1 and not _kmedoids:      # (--kmedoids keeps the matrix in a torch CUDA tensor)
+if int(os.environ.get("WORLD_SIZE", "1")) <= 1 and not _kmedoids and not _clip:      # (--kmedoids and the clip keep the matrix in a torch CUDA tensor)
     _lib.PREFER_NO_TORCH = True      # one process, one GPU: numpy + the host-pointer entry points of the C ABI are enough
 
 from .phyloligo import main  # noqa: E402

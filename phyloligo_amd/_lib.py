@@ -121,6 +121,8 @@ SIGNATURES = {
     "po_kmedoids": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _c.POINTER(PoKmedoidsResult)]),
     "po_kmedoids_costs_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _vp, _u64, _vp]),
     "po_kmedoids_assign_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _vp]),
+    "po_row_medians_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u64, _vp]),
+    "po_row_medians_passes": (_int, [_vp, _c.POINTER(_u64)]),
     "po_fasta_scan": (_int, [_vp, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),
     "po_fasta_extract": (_int, [_vp, _u64, _vp, _vp, _vp, _vp]),
     "po_file_read": (_int, [_cp, _vp, _u64]),

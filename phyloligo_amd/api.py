@@ -444,27 +444,28 @@ class Context:
         return (y, _tsne_stats(res, hist)) if want_stats else y
 
     # ---- k-medoids on a distance matrix --------------------------------------------------------
-    def _kmed_matrix(self, matrix):
-        """(is_torch, matrix, dtype code, n, ld) of a 2-D float32 / float64 matrix with unit inner stride and row stride >= n"""
+    def _kmed_matrix(self, matrix, square=True):
+        """(is_torch, matrix, dtype code, n, ld) of a 2-D float32 / float64 matrix with unit inner stride and row stride >= n;
+        square=False: any [rows, n] (the row count is matrix.shape[0])"""
         if _is_torch(matrix):
             import torch
             self._check_device(matrix)
-            if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1] or matrix.dtype not in (torch.float32, torch.float64):
-                raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must be a square float32 / float64 tensor (got %s %s)"
-                                          % (tuple(matrix.shape), matrix.dtype))
-            n = matrix.shape[0]
+            if matrix.dim() != 2 or (square and matrix.shape[0] != matrix.shape[1]) or matrix.dtype not in (torch.float32, torch.float64):
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must be a %s float32 / float64 tensor (got %s %s)"
+                                          % ("square" if square else "2-D", tuple(matrix.shape), matrix.dtype))
+            rows, n = matrix.shape
             if n > 1 and matrix.stride(1) != 1:
                 raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must have unit inner stride (strides %r)" % (tuple(matrix.stride()),))
-            ld = matrix.stride(0) if n > 1 else max(n, 1)
+            ld = matrix.stride(0) if rows > 1 else max(n, 1)
             return True, matrix, PO_F32 if matrix.dtype == torch.float32 else PO_F64, n, ld
         if not isinstance(matrix, np.ndarray) or matrix.dtype not in (np.float32, np.float64):
             matrix = np.asarray(matrix, dtype=np.float64)
-        if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1]:
-            raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must be square (got shape %r)" % (matrix.shape,))
-        n = matrix.shape[0]
-        if n > 1 and (matrix.strides[1] != matrix.itemsize or matrix.strides[0] % matrix.itemsize or matrix.strides[0] < 0):
+        if matrix.ndim != 2 or (square and matrix.shape[0] != matrix.shape[1]):
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "matrix must be %s (got shape %r)" % ("square" if square else "2-D", matrix.shape))
+        rows, n = matrix.shape
+        if (n > 1 or rows > 1) and (matrix.strides[1] != matrix.itemsize or matrix.strides[0] % matrix.itemsize or matrix.strides[0] < 0):
             matrix = np.ascontiguousarray(matrix)
-        ld = matrix.strides[0] // matrix.itemsize if n > 1 else max(n, 1)
+        ld = matrix.strides[0] // matrix.itemsize if rows > 1 else max(n, 1)
         return False, matrix, PO_F32 if matrix.dtype == np.float32 else PO_F64, n, ld
 
     def kmedoids(self, matrix, n_clusters=8, max_iter=300, init="heuristic", want_stats=False):
@@ -510,12 +511,12 @@ class Context:
                                      "assign_ms": res.assign_ms, "update_ms": res.update_ms}
         return labels, medoids
 
-    def _kmed_device(self, matrix):
+    def _kmed_device(self, matrix, square=True):
         import torch
-        is_t, matrix, code, n, ld = self._kmed_matrix(matrix)
+        is_t, matrix, code, n, ld = self._kmed_matrix(matrix, square)
         if not is_t:
             matrix = torch.from_numpy(matrix).cuda(self.device)      # a strided view arrives with its row stride
-            ld = matrix.stride(0) if n > 1 else max(n, 1)
+            ld = matrix.stride(0) if matrix.shape[0] > 1 else max(n, 1)
         return is_t, matrix, code, n, ld
 
     def kmedoids_costs(self, matrix, labels, rows=None):
@@ -561,6 +562,28 @@ class Context:
         check(self._lib.po_kmedoids_assign_dev(self._h, matrix.data_ptr(), code, n, ld, medoids.numel(), medoids.data_ptr(),
                                                labels.data_ptr()))
         return labels if is_t else labels.cpu().numpy()
+
+    # ---- row medians of a matrix (the reference's outlier clip) -----------------------------------
+    def row_medians(self, matrix):
+        """float64 [rows]: the median of every row of matrix [rows, n] (float32 / float64, unit inner stride, any row stride >= n),
+        over all n columns: numpy.median(matrix.astype(float64), axis=1), exactly - R's apply(dist_matrix, 1, median) of
+        bin/phyloselect.R:339-357 (po_row_medians_dev).  A row that holds a NaN gives NaN.  numpy in -> numpy out (the matrix is
+        copied to the device); torch CUDA tensor in -> tensor out on torch's current stream."""
+        import torch
+        is_t, matrix, code, n, ld = self._kmed_device(matrix, square=False)
+        rows = matrix.shape[0]
+        out = torch.empty((rows,), dtype=torch.float64, device=matrix.device)
+        self._use_torch_stream()
+        check(self._lib.po_row_medians_dev(self._h, matrix.data_ptr(), code, rows, n, ld, out.data_ptr()))
+        if n == 0:
+            out.fill_(float("nan"))                      # numpy.median of an empty row
+        return out if is_t else out.cpu().numpy()
+
+    def row_medians_passes(self):
+        """row reads of the last row_medians call, summed over its rows (po_row_medians_passes)"""
+        v = ctypes.c_uint64()
+        check(self._lib.po_row_medians_passes(self._h, ctypes.byref(v)))
+        return v.value
 
     def _pairwise(self, counts, totals, freq, metric, row_begin, row_end, dtype, symmetric, out, want_stats,
                   extra_flags=0):
@@ -622,6 +645,47 @@ class Context:
                          "pairs": stats.pairs, "tiles": stats.tiles, "kernel_id": stats.kernel_id,
                     "rc_folded": bool(stats.rc_folded)}
         return out
+
+
+def clip_threshold(medians, percentile):
+    """The reference's clip threshold quantile(medians, probs=percentile) (bin/phyloselect.R:341), R's default type 7: with x the
+    sorted medians and idx = (n - 1) * percentile, x[floor(idx)] when idx is whole, else the two neighbours interpolated.
+    Host arithmetic on n doubles.  PO_EINVAL: percentile outside [0, 1], no medians, a NaN among them (the message names the row)."""
+    x = np.asarray(medians, dtype=np.float64).ravel()
+    if not 0.0 <= percentile <= 1.0:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "clip percentile must lie in [0, 1] (got %r)" % (percentile,))
+    if x.size == 0:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "clip threshold of no medians")
+    bad = np.flatnonzero(np.isnan(x))
+    if bad.size:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "the median of row %d is NaN (the row holds a NaN, e.g. Bray-Curtis of an empty "
+                                                  "record): the clip cannot order it" % int(bad[0]))
+    x = np.sort(x)
+    idx = (x.size - 1) * float(percentile)
+    lo, hi = int(np.floor(idx)), int(np.ceil(idx))
+    h = idx - lo
+    if h == 0 or x[hi] == x[lo]:                         # (R interpolates only where the neighbours differ: ties at the threshold stay)
+        return float(x[lo])
+    return float((1.0 - h) * x[lo] + h * x[hi])
+
+
+def clip_keep(medians, percentile, lengths=None, min_size=0):
+    """int64 ascending indices of the records that survive the reference's two filters in its order (bin/phyloselect.R:339-357):
+    first medians <= clip_threshold(medians, percentile), skipped when percentile == 1; then lengths >= min_size among the
+    survivors, skipped when min_size == 0 (so a short record still takes part in the quantile)."""
+    med = np.asarray(medians, dtype=np.float64).ravel()
+    if not 0.0 <= percentile <= 1.0:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "clip percentile must lie in [0, 1] (got %r)" % (percentile,))
+    if min_size < 0:
+        raise _lib.PhyloligoError(_lib.PO_EINVAL, "min_size must not be negative (got %r)" % (min_size,))
+    keep = np.arange(med.size, dtype=np.int64)
+    if percentile != 1 and med.size:
+        keep = keep[med <= clip_threshold(med, percentile)]
+    if min_size != 0:
+        if lengths is None or len(lengths) != med.size:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "min_size needs the length of every record (%d medians)" % med.size)
+        keep = keep[np.asarray(lengths)[keep] >= min_size]
+    return keep
 
 
 def tsne_neighbours(n, perplexity):

@@ -82,6 +82,7 @@ struct po_ctx {
     double* h_tsne = nullptr;          // pinned: 8 doubles read back by the t-SNE entry points
     po_buf ws_kmed;                    // k-medoids: pair list (rows / medoids, labels / clusters), costs, per-cluster minima (po_kmedoids.hip)
     double* h_kmed = nullptr;          // pinned: 8 doubles read back by the k-medoids entry points
+    po_buf ws_rowmed;                  // row medians: the counter of row reads of the last call (po_rowmedian.hip)
     void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of the host-pointer entry points (device -> host rows)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
@@ -301,3 +302,25 @@ int po_launch_tsne_gradient(po_ctx* ctx, const int64_t* d_rowptr, const int32_t*
                             hipEvent_t* ev);   // ev (may be NULL): 4 events recorded before / after the repulsion, after Z, after the attraction
 
 static inline uint64_t po_round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
+
+// Order-preserving unsigned keys of the selection kernels (po_knn.hip, po_rowmedian.hip): float32 / float64 bits with the sign
+// folded in (negative: all bits flipped; positive: sign bit set), -0 read as +0 so that the two zeros tie as numbers do, every
+// NaN one key above +inf (PO_NAN_KEY; the key above it is the k-NN lists' "unused entry").  desc: the order of -v.
+#define PO_NAN_KEY (~0ull - 1)
+#if defined(__HIPCC__)
+__device__ inline uint64_t po_order_key(double v, bool desc) {
+    if (desc) v = -v;
+    if (v != v) return PO_NAN_KEY;
+    if (v == 0.0) v = 0.0;                  // -0 -> +0
+    const uint64_t b = static_cast<uint64_t>(__double_as_longlong(v));
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ inline uint64_t po_order_key(float v, bool desc) {
+    if (desc) v = -v;
+    if (v != v) return PO_NAN_KEY;
+    if (v == 0.0f) v = 0.0f;
+    const uint32_t b = __float_as_uint(v);
+    return static_cast<uint64_t>((b >> 31) ? ~b : (b | 0x80000000u));
+}
+#endif

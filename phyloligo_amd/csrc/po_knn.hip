@@ -27,24 +27,7 @@ namespace {
 constexpr uint32_t kThreads = 256;
 constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint64_t kEmptyKey = ~0ull;
-constexpr uint64_t kNanKey = ~0ull - 1;
 constexpr uint32_t kEmptyCol = 0xFFFFFFFFu;
-
-__device__ inline uint64_t order_key(double v, bool desc) {
-    if (desc) v = -v;
-    if (v != v) return kNanKey;
-    if (v == 0.0) v = 0.0;                  // -0 -> +0
-    const uint64_t b = static_cast<uint64_t>(__double_as_longlong(v));
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ inline uint64_t order_key(float v, bool desc) {
-    if (desc) v = -v;
-    if (v != v) return kNanKey;
-    if (v == 0.0f) v = 0.0f;
-    const uint32_t b = __float_as_uint(v);
-    return static_cast<uint64_t>((b >> 31) ? ~b : (b | 0x80000000u));
-}
 
 __device__ inline bool pair_less(uint64_t ka, uint32_t ca, uint64_t kb, uint32_t cb) {
     return ka < kb || (ka == kb && ca < cb);
@@ -79,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(int32_t* __restric
     const bool aligned = !ci && (reinterpret_cast<uintptr_t>(s) & 15u) == 0;
 
     const int32_t last = li[K - 1];
-    uint64_t thr_k = last < 0 ? kEmptyKey : order_key(lv[K - 1], desc != 0);
+    uint64_t thr_k = last < 0 ? kEmptyKey : po_order_key(lv[K - 1], desc != 0);
     uint32_t thr_c = last < 0 ? kEmptyCol : static_cast<uint32_t>(last);
     bool loaded = false;
     uint32_t cnt = 0;                                                      // entries in the buffer [Kp, Kp + cnt)
@@ -90,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(int32_t* __restric
             for (uint32_t j = tid; j < Kp; j += kThreads) {
                 const int32_t x = j < K ? li[j] : -1;
                 const T v = j < K ? lv[j] : T(0);
-                sk[j] = x < 0 ? kEmptyKey : order_key(v, desc != 0);
+                sk[j] = x < 0 ? kEmptyKey : po_order_key(v, desc != 0);
                 sc[j] = x < 0 ? kEmptyCol : static_cast<uint32_t>(x);
                 sv[j] = v;
             }
@@ -151,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(int32_t* __restric
         for (uint32_t u = 0; u < V; ++u) {
             const uint32_t e = e0 + u;
             const int32_t c = e < len ? (ci ? ci[e] : static_cast<int32_t>(col0 + e)) : -1;
-            key[u] = order_key(v[u], desc != 0);
+            key[u] = po_order_key(v[u], desc != 0);
             col[u] = static_cast<uint32_t>(c);
             ok[u] = c >= 0 && !(diag && static_cast<uint64_t>(c) == r) && pair_less(key[u], col[u], thr_k, thr_c);
             const uint64_t m = __ballot(ok[u]);

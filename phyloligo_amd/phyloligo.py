@@ -41,15 +41,16 @@ class ProfileMatrix(np.ndarray):
     """float64[N, 4^k] frequencies exactly as compute_frequencies_joblib returns them
     (phyloligo.py:847-877), carrying the exact integer profile they were derived from."""
 
-    def __new__(cls, freq, counts=None, totals=None, titles=None):
+    def __new__(cls, freq, counts=None, totals=None, titles=None, lengths=None):
         obj = np.asarray(freq, dtype=np.float64).view(cls)
         obj.counts, obj.totals, obj.titles = counts, totals, titles
+        obj.lengths = lengths                            # int64[N]: bases of every record as ingested (--min-size)
         return obj
 
     def __array_finalize__(self, obj):
         if obj is None:
             return
-        self.counts = self.totals = self.titles = None   # slices/copies are plain frequencies
+        self.counts = self.totals = self.titles = self.lengths = None   # slices/copies are plain frequencies
 
 
 def read_fasta(genome):
@@ -119,6 +120,7 @@ def compute_frequencies(mthdrun, large, genome, pattern, strand, distchunksize=2
         mark("frequencies_d2h_ms")
         counts = d_counts.cpu().numpy().view(np.uint32)
         totals = d_totals.cpu().numpy().view(np.uint64)
+        lengths = np.diff(d_off.cpu().numpy().astype(np.int64))
         mark("counts_d2h_ms")
     else:
         seq, offsets, titles = read_fasta(genome)
@@ -126,8 +128,9 @@ def compute_frequencies(mthdrun, large, genome, pattern, strand, distchunksize=2
         counts, totals = ctx.count_profiles(seq, offsets, pattern, strand)
         mark("stage1_host_pointers_ms")
         freq = ctx.frequencies(counts, totals)
+        lengths = np.diff(np.asarray(offsets).astype(np.int64))
         mark("count2freq_host_pointers_ms")
-    result = ProfileMatrix(freq, counts, totals, titles)
+    result = ProfileMatrix(freq, counts, totals, titles, lengths)
     mark("wrap_ms")
     LAST_INGEST = phases
     return result, None
@@ -412,9 +415,44 @@ def get_cmd(argv=None):
     parser.add_argument("--kmedoids-dtype", action="store", dest="kmedoids_dtype", choices=["float64", "float32"], default="float64",
                         help="with --kmedoids: element type of the matrix in GPU memory; float32 takes half the memory, sums are "
                              "float64 either way [default:%(default)s]")
+    parser.add_argument("--clip-percentile", action="store", dest="clip_percentile", type=float, default=1.0, metavar="P",
+                        help="not in the reference's phyloligo.py: before anything is computed from the matrix, drop the contigs whose "
+                             "median distance to all contigs lies above the P quantile of those medians (what phyloselect.R -c P "
+                             "does to the matrix file; its help suggests 0.97); the medians are taken in GPU memory and the run "
+                             "continues as if the input held only the kept contigs; 0 <= P <= 1 [default:%(default)g = off]")
+    parser.add_argument("--min-size", action="store", dest="min_size", type=int, default=0, metavar="L",
+                        help="after --clip-percentile: drop the contigs shorter than L bases (phyloselect.R -s L) "
+                             "[default:%(default)d = off]")
+    parser.add_argument("--clip-out", action="store", dest="clip_out", default=None, metavar="FILE",
+                        help="with --clip-percentile / --min-size: write one line per kept contig to FILE: its 0-based index in the "
+                             "input, the first word of its title, its length and its median distance, tab separated")
     params = parser.parse_args(argv)
     params.workdir = os.path.abspath(params.workdir)
     return params
+
+
+def _clip_active(params):
+    return getattr(params, "clip_percentile", 1.0) != 1 or getattr(params, "min_size", 0) != 0
+
+
+def _clip_refused(params):
+    """the reason --clip-percentile / --min-size cannot run with these options, or None"""
+    p, size = getattr(params, "clip_percentile", 1.0), getattr(params, "min_size", 0)
+    if not 0.0 <= p <= 1.0:
+        return "Error, --clip-percentile P needs 0 <= P <= 1 (got %g)" % p
+    if size < 0:
+        return "Error, --min-size L needs L >= 0 bases (got %d)" % size
+    if not _clip_active(params):
+        if getattr(params, "clip_out", None) is not None:
+            return "Error, --clip-out lists the contigs a filter keeps: give --clip-percentile P < 1 or --min-size L > 0 with it"
+        return None
+    if params.dist == "KT":
+        return "Error, --clip-percentile / --min-size need a distance: -d KT is a correlation (a large median does not mean distant)"
+    if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "Error, --clip-percentile / --min-size run on one GPU: a clip over several ranks (--gpus N > 1) is out of scope"
+    if params.mthdrun not in ("joblib", "hip"):
+        return "Error, --clip-percentile / --min-size support --method joblib|hip"
+    return None
 
 
 def _knn_refused(params):
@@ -505,7 +543,7 @@ def main_distributed(params):
             sys.exit(1)
     if params.strand not in STRANDS or params.dist not in METRICS:
         sys.exit(1)
-    for refused in (_kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
+    for refused in (_clip_refused(params), _kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
         if refused:
             if rank == 0:
                 print(refused, file=sys.stderr)
@@ -682,7 +720,7 @@ def main(argv=None):
         params.pattern = str("1") * params.pattern
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return main_distributed(params)
-    for refused in (_kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
+    for refused in (_clip_refused(params), _kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
         if refused:
             print(refused, file=sys.stderr)
             sys.exit(1)
@@ -697,6 +735,8 @@ def main(argv=None):
                                                  params.strand, params.distchunksize, params.threads_max,
                                                  params.workdir)
     t_freq = time.perf_counter()
+    if _clip_active(params):
+        frequencies = _clip(params, frequencies)
     print("Computing Pairwise distances")
     t_dist0 = time.perf_counter()
     if params.kmedoids is not None:
@@ -743,6 +783,87 @@ def _knn_single(params, frequencies, t_start, t_freq, t_dist0):
     if params.json_stats:
         _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
     return 0
+
+
+LAST_CLIP = None         # the clip_* keys of the last --clip-percentile / --min-size run (what --json-stats reports)
+
+
+def _device_matrix(params, ctx, frequencies, f32, who):
+    """the dense n x n matrix of the run's metric in device memory (po_pairwise_dev), rows on whole 128-byte lines: (buffer, ld,
+    stage-2 stats); exits with the sizes when it does not fit"""
+    import torch
+    n = frequencies.shape[0]
+    dev = torch.device("cuda", ctx.device)
+    esz = 4 if f32 else 8
+    name = "float32" if f32 else "float64"
+    ld = (n + 128 // esz - 1) // (128 // esz) * (128 // esz)
+    try:
+        buf = torch.empty((n, ld), dtype=torch.float32 if f32 else torch.float64, device=dev)
+    except torch.cuda.OutOfMemoryError:
+        print("Error, %s: the %d x %d %s matrix (%.1f GB) does not fit the memory of the GPU%s"
+              % (who, n, n, name, n * ld * esz / 1e9, "" if f32 else "; a float32 matrix takes half (%.1f GB)" % (n * ld * 4 / 1e9)),
+              file=sys.stderr)
+        sys.exit(1)
+    d_counts = torch.from_numpy(np.ascontiguousarray(frequencies.counts).view(np.int32)).to(dev)
+    d_totals = torch.from_numpy(np.ascontiguousarray(frequencies.totals).view(np.int64)).to(dev)
+    _, st = ctx.pairwise(d_counts, d_totals, params.dist, dtype=name, out=buf, want_stats=True)
+    torch.cuda.synchronize(dev)
+    return buf, ld, st
+
+
+def _clip(params, frequencies):
+    """--clip-percentile / --min-size (bin/phyloselect.R:339-357): the dense matrix computed into device memory, its row medians
+    taken there (po_row_medians_dev), the two filters applied to those n doubles on the host; returns the profiles of the kept
+    records, in input order - everything after this runs as it would on an input that held only them."""
+    global LAST_CLIP
+    if frequencies is None:
+        return None
+    if params.dist not in METRICS:
+        print("Error, unknown metric methodfor joblib: {}".format(params.dist), file=sys.stderr)
+        sys.exit(1)
+    import torch
+    print("Clipping outlier contigs")
+    n = frequencies.shape[0]
+    ctx = _context()
+    f32 = params.large in ("memmap", "h5py") or params.kmedoids_dtype == "float32"      # the run's output is float32 data anyway
+    t0 = time.perf_counter()
+    medians = np.zeros(0)
+    t1 = t2 = t0
+    if n:
+        buf, _, _ = _device_matrix(params, ctx, frequencies, f32, "--clip-percentile")
+        t1 = time.perf_counter()
+        d_med = ctx.row_medians(buf[:, :n])
+        torch.cuda.synchronize(d_med.device)
+        t2 = time.perf_counter()
+        medians = d_med.cpu().numpy()
+        del buf, d_med
+        torch.cuda.empty_cache()                         # the matrix of the kept records is computed afresh: give the room back
+    lengths = np.asarray(frequencies.lengths, dtype=np.int64)
+    p, size = params.clip_percentile, params.min_size
+    try:
+        by_median = api.clip_keep(medians, p)
+        keep = api.clip_keep(medians, p, lengths, size)
+        threshold = api.clip_threshold(medians, p) if p != 1 and n else None
+    except api._lib.PhyloligoError as e:
+        print("Error, --clip-percentile: %s" % e, file=sys.stderr)
+        sys.exit(1)
+    LAST_CLIP = {"clip_percentile": p, "clip_min_size": size, "clip_threshold": threshold, "clip_kept": int(keep.size),
+                 "clip_dropped_by_median": int(n - by_median.size), "clip_dropped_by_size": int(by_median.size - keep.size),
+                 "clip_medians_ms": (t2 - t1) * 1e3, "clip_matrix_ms": (t1 - t0) * 1e3, "clip_dtype": "float32" if f32 else "float64",
+                 "clip_input_contigs": int(n)}
+    if keep.size < 1:
+        print("Error, --clip-percentile %g --min-size %d keep none of the %d contigs" % (p, size, n), file=sys.stderr)
+        sys.exit(1)
+    titles = frequencies.titles
+    downstream_runs = ((params.kmedoids is None or params.kmedoids <= keep.size) and (params.tsne is None or keep.size >= 4) and
+                       (params.knn is None or params.knn < keep.size))
+    if params.clip_out and downstream_runs:              # (a run its mode refuses for the kept count leaves no file behind)
+        with open(params.clip_out, "w") as fh:
+            for i in keep:
+                words = titles[int(i)].split()
+                fh.write("%d\t%s\t%d\t%.17g\n" % (i, words[0] if words else "", lengths[i], medians[i]))
+    return ProfileMatrix(np.asarray(frequencies)[keep], frequencies.counts[keep], frequencies.totals[keep],
+                         [titles[int(i)] for i in keep], lengths[keep])
 
 
 LAST_TSNE = None         # tsne_ms / tsne_iterations / tsne_kl of the last --tsne run (what --json-stats reports)
@@ -863,6 +984,7 @@ def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpu
                 {"knn": params.knn, "knn_select_ms": None if LAST_STAGE2 is None else LAST_STAGE2.get("select_ms")}),
              **({} if getattr(params, "tsne", None) is None or LAST_TSNE is None else dict(LAST_TSNE, tsne_perplexity=params.tsne)),
              **({} if getattr(params, "kmedoids", None) is None or LAST_KMEDOIDS is None else LAST_KMEDOIDS),
+             **({} if not _clip_active(params) or LAST_CLIP is None else LAST_CLIP),
              "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
     with open(params.json_stats, "w") as fh:
         json.dump(stats, fh, indent=1)
