@@ -360,6 +360,45 @@ int po_kmedoids_costs_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t
 int po_kmedoids_assign_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, uint32_t n_clusters,
                            const int32_t* d_medoids, int32_t* d_labels);
 
+/* ---- silhouettes of a clustering of the distance matrix: is K a good choice, which records sit between two clusters ------------ *
+ * What sklearn.metrics.silhouette_samples(matrix, labels, metric="precomputed") computes, the score the scikit-learn stack under
+ * phyloselect.py offers for the question its --interactive loop ("perform an other run? ... change nbk") leaves to the user's eye.
+ * matrix: as for k-medoids ([n][n] float32 / float64, ld >= n elements, read by rows, never written); the diagonal is expected to
+ * be 0.  d_labels: int32 [n], every value in 0 .. n_clusters-1 (checked on the device: PO_EINVAL names the first position outside).
+ *   sizes[c]   the number of columns with label c
+ *   S[i][c]    the float64 sum of matrix[i][j] over the columns j with label c: every entry widened to float64 before it is added,
+ *              the row taken as stored (matrix[i][i] included, as scikit-learn includes it), an entry of another cluster replaced by
+ *              +0 with a select and never multiplied, so a NaN outside a cluster stays outside it.  Summed in the order of the
+ *              k-medoids row sums: S[i][d_labels[i]] has the bytes po_kmedoids_costs_dev gives for row i, and the bytes of S[i][c]
+ *              depend on row i, the labels and n alone - not on n_clusters, ld, the alignment or the other rows.
+ *   s[i]       with own = d_labels[i]: 0 when sizes[own] == 1; otherwise a = S[i][own] / (sizes[own] - 1), b = the smallest
+ *              S[i][c] / sizes[c] over c != own with sizes[c] > 0, m = max(a, b), s = (b - a) / m, or 0 when m == 0 (duplicate
+ *              records; scikit-learn's nan_to_num of 0 / 0 gives 0 too).
+ *   NaN        if S[i][c] of any non-empty cluster is NaN, s[i] is NaN (a cluster of one included) and so is the mean.  scikit-learn
+ *              prints 0 there; a silent 0 for a record whose distance is undefined is worse than NaN.
+ *   empty      clusters without a member (k-medoids can return them) are skipped; fewer than two non-empty clusters: PO_EINVAL
+ *              (scikit-learn raises).
+ *   mean       (sum of s[i]) / n, a float64 sum with a fixed reduction tree.  No floating-point atomics anywhere.
+ * The clusters are handled PO_SILHOUETTE_CHUNK at a time: n_clusters <= PO_SILHOUETTE_CHUNK reads the matrix once, a larger
+ * n_clusters ceil(n_clusters / PO_SILHOUETTE_CHUNK) times; the n x n_clusters sums are never stored by po_silhouette* (workspace:
+ * n x PO_SILHOUETTE_CHUNK doubles, held by the context).  Every entry point synchronises the stream once, for the label check.
+ * po_cluster_sums_dev: d_sums [n][n_clusters] = S, for any 1 <= n_clusters <= n (no rule about empty clusters applies).
+ *   d_values float64 [n] = s     result (may be NULL; asking for it adds device events and one more synchronisation per pass)    */
+#define PO_SILHOUETTE_CHUNK 16
+int po_cluster_sums_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, const int32_t* d_labels,
+                        uint32_t n_clusters, double* d_sums);
+typedef struct po_silhouette_result {
+    double mean;                   /* (sum of the n values) / n */
+    uint32_t nonempty_clusters;    /* clusters with at least one member */
+    uint32_t passes;               /* matrix reads made: ceil(n_clusters / PO_SILHOUETTE_CHUNK) */
+    double sums_ms, finish_ms;     /* HIP-event times: the passes over the matrix; everything else (histogram, folds, the values) */
+} po_silhouette_result;
+int po_silhouette_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, const int32_t* d_labels, uint32_t n_clusters,
+                      double* d_values, po_silhouette_result* result);
+/* Host pointers: the matrix is copied to the device (PO_ENOMEM, with the size in the message, when it does not fit). */
+int po_silhouette(po_ctx* ctx, const void* matrix, int dtype, uint64_t n, uint64_t ld, const int32_t* labels, uint32_t n_clusters,
+                  double* values, po_silhouette_result* result);
+
 /* ---- row medians of a matrix in HBM ---------------------------------------------------------- *
  * d_out[i] = median of row i of d_matrix [rows][n] (float32 / float64, row major, leading dimension ld >= n elements; read,
  * never written), over all n columns - the diagonal of a distance matrix included: R's apply(dist_matrix, 1, median), the first

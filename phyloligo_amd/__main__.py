@@ -22,9 +22,11 @@ if _n > 1 and any(a == "--tsne" or a.startswith("--tsne=") for a in sys.argv[1:]
     # refused before any rank is started (phyloligo._tsne_refused says the same inside a rank)
     sys.stderr.write("Error, --tsne runs on one GPU: an embedding over several ranks (--gpus N > 1) is out of scope\n")
     sys.exit(1)
-_kmedoids = any(a == "--kmedoids" or a.startswith("--kmedoids=") for a in sys.argv[1:])
+_sweep = any(a == "--kmedoids-sweep" or a.startswith("--kmedoids-sweep=") for a in sys.argv[1:])
+_kmedoids = _sweep or any(a == "--kmedoids" or a.startswith("--kmedoids=") for a in sys.argv[1:])
 if _n > 1 and _kmedoids:
-    sys.stderr.write("Error, --kmedoids runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope\n")
+    sys.stderr.write("Error, %s runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope\n"
+                     % ("--kmedoids-sweep" if _sweep else "--kmedoids"))
     sys.exit(1)
 
 

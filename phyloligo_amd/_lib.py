@@ -69,6 +69,14 @@ class PoKmedoidsResult(ctypes.Structure):
                 ("rowsum_ms", ctypes.c_double), ("assign_ms", ctypes.c_double), ("update_ms", ctypes.c_double)]
 
 
+class PoSilhouetteResult(ctypes.Structure):
+    _fields_ = [("mean", ctypes.c_double), ("nonempty_clusters", ctypes.c_uint32), ("passes", ctypes.c_uint32),
+                ("sums_ms", ctypes.c_double), ("finish_ms", ctypes.c_double)]
+
+
+PO_SILHOUETTE_CHUNK = 16     # clusters per matrix read of the silhouette entry points (include/phyloligo_amd.h)
+
+
 class PhyloligoError(RuntimeError):
     def __init__(self, status, message):
         super().__init__("phyloligo_amd: %s (status %d)" % (message, status))
@@ -121,6 +129,9 @@ SIGNATURES = {
     "po_kmedoids": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _u32, _vp, _vp, _c.POINTER(PoKmedoidsResult)]),
     "po_kmedoids_costs_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _vp, _u64, _vp]),
     "po_kmedoids_assign_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u32, _vp, _vp]),
+    "po_cluster_sums_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _u32, _vp]),
+    "po_silhouette_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _u32, _vp, _c.POINTER(PoSilhouetteResult)]),
+    "po_silhouette": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _u32, _vp, _c.POINTER(PoSilhouetteResult)]),
     "po_row_medians_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u64, _vp]),
     "po_row_medians_passes": (_int, [_vp, _c.POINTER(_u64)]),
     "po_fasta_scan": (_int, [_vp, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),

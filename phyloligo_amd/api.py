@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoKmedoidsResult, PoStats, PoTsneParams, PoTsneResult,
+from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoKmedoidsResult, PoSilhouetteResult, PoStats, PoTsneParams, PoTsneResult,
                    check)
 
 
@@ -562,6 +562,70 @@ class Context:
         check(self._lib.po_kmedoids_assign_dev(self._h, matrix.data_ptr(), code, n, ld, medoids.numel(), medoids.data_ptr(),
                                                labels.data_ptr()))
         return labels if is_t else labels.cpu().numpy()
+
+    # ---- silhouettes of a clustering of a distance matrix -------------------------------------------
+    def _sil_clusters(self, labels, n, n_clusters):
+        """the cluster count of a call: n_clusters, or max(labels) + 1 when it is None"""
+        if n_clusters is None:
+            if labels.shape[0] == 0:
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels are empty")
+            n_clusters = int(labels.max()) + 1
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= n:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "n_clusters must be an integer in 1..n = %d (got %r)" % (n, n_clusters))
+        return int(n_clusters)
+
+    def _sil_device_labels(self, labels, n, dev):
+        import torch
+        labels = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+        self._check_device(labels)
+        if labels.dtype != torch.int32 or labels.shape != (n,):
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels must be int32 [%d] (got %s %s)" % (n, labels.dtype, tuple(labels.shape)))
+        return labels.contiguous()
+
+    def cluster_sums(self, matrix, labels, n_clusters=None):
+        """float64 [n, n_clusters]: S[i, c] = the sum of matrix[i, j] over the columns j with labels[j] == c, in float64 and in
+        the order of the k-medoids row sums (po_cluster_sums_dev): S[i, labels[i]] has the bytes of kmedoids_costs, and a
+        column's bytes do not depend on n_clusters.  labels: int32 [n] in 0..n_clusters-1 (checked); n_clusters=None means
+        max(labels) + 1.  Takes a torch CUDA tensor (numpy is copied to the device) and returns a torch CUDA tensor."""
+        import torch
+        _, matrix, code, n, ld = self._kmed_device(matrix)
+        labels = self._sil_device_labels(labels, n, matrix.device)
+        k = self._sil_clusters(labels, n, n_clusters)
+        out = torch.empty((n, k), dtype=torch.float64, device=matrix.device)
+        self._use_torch_stream()
+        check(self._lib.po_cluster_sums_dev(self._h, matrix.data_ptr(), code, n, ld, labels.data_ptr(), k, out.data_ptr()))
+        return out
+
+    def silhouette(self, matrix, labels, n_clusters=None, want_stats=False):
+        """float64 [n]: the silhouette value of every record for a precomputed distance matrix [n, n] and labels int32 [n] in
+        0..n_clusters-1 - sklearn.metrics.silhouette_samples(matrix, labels, metric="precomputed"), with float64 sums, except
+        that clusters without a member are skipped and a record with a NaN sum over a non-empty cluster gets NaN where
+        scikit-learn prints 0 (include/phyloligo_amd.h has the definitions).  n_clusters=None means max(labels) + 1; fewer
+        than two non-empty clusters are refused.  numpy in -> numpy out (po_silhouette: the matrix is copied to the device);
+        torch CUDA tensor in -> tensor out on torch's current stream (po_silhouette_dev).  want_stats: also a dict (mean,
+        nonempty_clusters, passes = matrix reads made, sums_ms, finish_ms)."""
+        is_t, matrix, code, n, ld = self._kmed_matrix(matrix)
+        res = PoSilhouetteResult()
+        rp = ctypes.byref(res) if want_stats else None
+        if is_t:
+            import torch
+            labels = self._sil_device_labels(labels, n, matrix.device)
+            k = self._sil_clusters(labels, n, n_clusters)
+            values = torch.empty((n,), dtype=torch.float64, device=matrix.device)
+            self._use_torch_stream()
+            check(self._lib.po_silhouette_dev(self._h, matrix.data_ptr(), code, n, ld, labels.data_ptr(), k, values.data_ptr(), rp))
+        else:
+            labels = labels.cpu().numpy() if _is_torch(labels) else np.asarray(labels)
+            if labels.shape != (n,) or labels.dtype.kind not in "iu":
+                raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels must be %d integers (got %s %r)" % (n, labels.dtype, labels.shape))
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            k = self._sil_clusters(labels, n, n_clusters)
+            values = np.zeros(n, dtype=np.float64)
+            check(self._lib.po_silhouette(self._h, _np_ptr(matrix), code, n, ld, _np_ptr(labels), k, _np_ptr(values), rp))
+        if want_stats:
+            return values, {"mean": res.mean, "nonempty_clusters": res.nonempty_clusters, "passes": res.passes,
+                            "sums_ms": res.sums_ms, "finish_ms": res.finish_ms}
+        return values
 
     # ---- row medians of a matrix (the reference's outlier clip) -----------------------------------
     def row_medians(self, matrix):

@@ -83,6 +83,8 @@ struct po_ctx {
     po_buf ws_kmed;                    // k-medoids: pair list (rows / medoids, labels / clusters), costs, per-cluster minima (po_kmedoids.hip)
     double* h_kmed = nullptr;          // pinned: 8 doubles read back by the k-medoids entry points
     po_buf ws_rowmed;                  // row medians: the counter of row reads of the last call (po_rowmedian.hip)
+    po_buf ws_sil;                     // silhouettes: labels, cluster sizes, one pass's sums [n][PO_SILHOUETTE_CHUNK], two doubles per row (po_silhouette.hip)
+    double* h_sil = nullptr;           // pinned: 8 doubles read back by the silhouette entry points
     void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of the host-pointer entry points (device -> host rows)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };

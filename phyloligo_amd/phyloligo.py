@@ -415,6 +415,18 @@ def get_cmd(argv=None):
     parser.add_argument("--kmedoids-dtype", action="store", dest="kmedoids_dtype", choices=["float64", "float32"], default="float64",
                         help="with --kmedoids: element type of the matrix in GPU memory; float32 takes half the memory, sums are "
                              "float64 either way [default:%(default)s]")
+    parser.add_argument("--kmedoids-sweep", action="store", dest="kmedoids_sweep", default=None, metavar="LO:HI",
+                        help="not in the reference's phyloligo.py: compute the matrix once, cluster it with k-medoids for every K in "
+                             "LO..HI, score every clustering by its mean silhouette and write the labels of the best K to -o (the "
+                             "largest mean wins, a tie goes to the smaller K): phyloselect.py --interactive's \"change nbk\" loop "
+                             "without the person; 2 <= LO <= HI <= N; honours --kmedoids-iter and --kmedoids-dtype")
+    parser.add_argument("--sweep-out", action="store", dest="sweep_out", default=None, metavar="FILE",
+                        help="with --kmedoids-sweep: write one tab-separated line per K to FILE: K, iterations, converged, empty "
+                             "clusters, inertia, mean silhouette and the cluster sizes")
+    parser.add_argument("--silhouette", action="store", dest="silhouette", default=None, metavar="FILE",
+                        help="with --kmedoids or --kmedoids-sweep: write the silhouette value of every contig for the labels written to "
+                             "-o to FILE, one per line in input order (sklearn.metrics.silhouette_samples on the matrix in GPU memory; "
+                             "a value near 0 or below marks a contig between two clusters)")
     parser.add_argument("--clip-percentile", action="store", dest="clip_percentile", type=float, default=1.0, metavar="P",
                         help="not in the reference's phyloligo.py: before anything is computed from the matrix, drop the contigs whose "
                              "median distance to all contigs lies above the P quantile of those medians (what phyloselect.R -c P "
@@ -490,24 +502,57 @@ def _tsne_refused(params):
     return None
 
 
+def parse_sweep(text):
+    """(LO, HI) of --kmedoids-sweep LO:HI, 2 <= LO <= HI; ValueError says what is wrong"""
+    parts = str(text).split(":")
+    try:
+        if len(parts) != 2:
+            raise ValueError
+        lo, hi = (int(q) for q in parts)
+    except ValueError:
+        raise ValueError("--kmedoids-sweep LO:HI needs two integers separated by a colon (got %r)" % (text,)) from None
+    if not 2 <= lo <= hi:
+        raise ValueError("--kmedoids-sweep LO:HI needs 2 <= LO <= HI <= number of contigs (got %d:%d)" % (lo, hi))
+    return lo, hi
+
+
+def _sweep_range(params):
+    """(LO, HI) of a --kmedoids-sweep run that passed _kmedoids_refused, else None"""
+    text = getattr(params, "kmedoids_sweep", None)
+    return None if text is None else parse_sweep(text)
+
+
 def _kmedoids_refused(params):
-    """the reason --kmedoids cannot run with these options, or None"""
-    if getattr(params, "kmedoids", None) is None:
+    """the reason --kmedoids / --kmedoids-sweep (and --silhouette, --sweep-out with them) cannot run with these options, or None"""
+    sweep = getattr(params, "kmedoids_sweep", None)
+    if getattr(params, "sweep_out", None) is not None and sweep is None:
+        return "Error, --sweep-out lists the runs of a sweep: give --kmedoids-sweep LO:HI with it"
+    if getattr(params, "kmedoids", None) is None and sweep is None:
+        if getattr(params, "silhouette", None) is not None:
+            return "Error, --silhouette scores a clustering: give --kmedoids K or --kmedoids-sweep LO:HI with it"
         return None
+    who = "--kmedoids" if sweep is None else "--kmedoids-sweep"
+    if sweep is not None:
+        if params.kmedoids is not None:
+            return "Error, --kmedoids-sweep tries every K of its range: it cannot be combined with --kmedoids %d" % params.kmedoids
+        try:
+            parse_sweep(sweep)
+        except ValueError as e:
+            return "Error, %s" % e
     if params.knn is not None or getattr(params, "tsne", None) is not None:
-        return ("Error, --kmedoids writes cluster labels to -o, --knn a neighbour graph and --tsne an embedding: give one of them")
+        return ("Error, %s writes cluster labels to -o, --knn a neighbour graph and --tsne an embedding: give one of them" % who)
     if params.large != "None":
-        return "Error, --kmedoids writes one label per contig as text, not a matrix container: it cannot be combined with --large %s" % params.large
+        return "Error, %s writes one label per contig as text, not a matrix container: it cannot be combined with --large %s" % (who, params.large)
     if params.dist == "KT":
-        return "Error, --kmedoids needs a distance: -d KT is a correlation (larger means closer)"
-    if params.kmedoids < 1:
+        return "Error, %s needs a distance: -d KT is a correlation (larger means closer)" % who
+    if sweep is None and params.kmedoids < 1:
         return "Error, --kmedoids K needs 1 <= K <= number of contigs (got %d)" % params.kmedoids
     if params.kmedoids_iter < 1:
         return "Error, --kmedoids-iter needs at least 1 iteration (got %d)" % params.kmedoids_iter
     if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "Error, --kmedoids runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope"
+        return "Error, %s runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope" % who
     if params.mthdrun not in ("joblib", "hip"):
-        return "Error, --kmedoids supports --method joblib|hip"
+        return "Error, %s supports --method joblib|hip" % who
     return None
 
 
@@ -739,7 +784,7 @@ def main(argv=None):
         frequencies = _clip(params, frequencies)
     print("Computing Pairwise distances")
     t_dist0 = time.perf_counter()
-    if params.kmedoids is not None:
+    if params.kmedoids is not None or params.kmedoids_sweep is not None:
         return _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0)
     if params.tsne is not None:
         return _tsne_single(params, frequencies, t_start, t_freq, t_dist0)
@@ -855,8 +900,9 @@ def _clip(params, frequencies):
         print("Error, --clip-percentile %g --min-size %d keep none of the %d contigs" % (p, size, n), file=sys.stderr)
         sys.exit(1)
     titles = frequencies.titles
-    downstream_runs = ((params.kmedoids is None or params.kmedoids <= keep.size) and (params.tsne is None or keep.size >= 4) and
-                       (params.knn is None or params.knn < keep.size))
+    sweep = _sweep_range(params)
+    downstream_runs = ((params.kmedoids is None or params.kmedoids <= keep.size) and (sweep is None or sweep[1] <= keep.size) and
+                       (params.tsne is None or keep.size >= 4) and (params.knn is None or params.knn < keep.size))
     if params.clip_out and downstream_runs:              # (a run its mode refuses for the kept count leaves no file behind)
         with open(params.clip_out, "w") as fh:
             for i in keep:
@@ -910,18 +956,62 @@ def write_labels(path, labels):
         fh.write("".join("%d\n" % int(x) for x in labels))
 
 
+def write_silhouette(path, values):
+    """one silhouette value per contig, in input order: n lines, each repr(float(value)) and a line feed"""
+    with open(path, "w") as fh:
+        fh.write("".join("%r\n" % float(x) for x in values))
+
+
+SWEEP_COLUMNS = ("K", "iterations", "converged", "empty_clusters", "inertia", "silhouette_mean", "sizes")
+
+
+def write_sweep_table(path, rows):
+    """the runs of a --kmedoids-sweep, one tab-separated line per K behind one '#' header line: K, iterations, converged (1 / 0),
+    empty_clusters, repr of the inertia, repr of the mean silhouette, the cluster sizes joined by commas"""
+    with open(path, "w") as fh:
+        fh.write("#" + "\t".join(SWEEP_COLUMNS) + "\n")
+        for r in rows:
+            fh.write("%d\t%d\t%d\t%d\t%r\t%r\t%s\n" % (r["K"], r["iterations"], 1 if r["converged"] else 0, r["empty_clusters"],
+                                                         float(r["inertia"]), float(r["silhouette_mean"]), ",".join("%d" % x for x in r["sizes"])))
+
+
+def sweep_best(rows):
+    """the row of a sweep that wins: the largest mean silhouette, a tie goes to the smaller K, a NaN never wins; None if all are NaN"""
+    best = None
+    for r in sorted(rows, key=lambda r: r["K"]):
+        m = r["silhouette_mean"]
+        if m == m and (best is None or m > best["silhouette_mean"]):
+            best = r
+    return best
+
+
+def silhouette_cluster_means(values, labels, k):
+    """per cluster the mean of its members' silhouette values (host, float64), None for a cluster without a member"""
+    values, labels = np.asarray(values, dtype=np.float64), np.asarray(labels)
+    return [float(values[labels == c].mean()) if (labels == c).any() else None for c in range(k)]
+
+
 def _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0):
-    """--kmedoids: the dense matrix computed into device memory (po_pairwise_dev), clustered there (po_kmedoids_dev); only the
-    labels come back"""
+    """--kmedoids / --kmedoids-sweep: the dense matrix computed into device memory (po_pairwise_dev) once, clustered there
+    (po_kmedoids_dev) for the one K or for every K of the range, each clustering scored there (po_silhouette_dev) when the run
+    reports it; only labels, silhouette values and scalars come back"""
     global LAST_STAGE2, LAST_KMEDOIDS
     if frequencies is None:
         return 0
     import torch
     n = frequencies.shape[0]
-    k = params.kmedoids
-    if not 1 <= k <= n:
-        print("Error, --kmedoids K needs 1 <= K <= number of contigs (got K = %d for %d contigs)" % (k, n), file=sys.stderr)
-        sys.exit(1)
+    sweep = _sweep_range(params)
+    if sweep is None:
+        ks_wanted = [params.kmedoids]
+        if not 1 <= params.kmedoids <= n:
+            print("Error, --kmedoids K needs 1 <= K <= number of contigs (got K = %d for %d contigs)" % (params.kmedoids, n), file=sys.stderr)
+            sys.exit(1)
+    else:
+        ks_wanted = list(range(sweep[0], sweep[1] + 1))
+        if sweep[1] > n:
+            print("Error, --kmedoids-sweep LO:HI needs 2 <= LO <= HI <= number of contigs (got %d:%d for %d contigs)" % (sweep[0], sweep[1], n),
+                  file=sys.stderr)
+            sys.exit(1)
     ctx = _context()
     dev = torch.device("cuda", ctx.device)
     f32 = params.kmedoids_dtype == "float32"
@@ -939,24 +1029,61 @@ def _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0):
     _, st = ctx.pairwise(d_counts, d_totals, params.dist, dtype=params.kmedoids_dtype, out=buf, want_stats=True)
     LAST_STAGE2 = dict(st, rows=[0, n])
     torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    try:
-        labels, medoids, ks = ctx.kmedoids(buf[:, :n], k, max_iter=params.kmedoids_iter, want_stats=True)
-    except api._lib.PhyloligoError as e:
-        print("Error, --kmedoids: %s" % e, file=sys.stderr)
-        sys.exit(1)
-    labels, medoids = labels.cpu().numpy(), medoids.cpu().numpy()
+    scored = sweep is not None or params.silhouette is not None or bool(params.json_stats)      # the mean costs one matrix read
+    runs = []
+    for k in ks_wanted:
+        t0 = time.perf_counter()
+        try:
+            d_labels, medoids, ks = ctx.kmedoids(buf[:, :n], k, max_iter=params.kmedoids_iter, want_stats=True)
+        except api._lib.PhyloligoError as e:
+            print("Error, --kmedoids: %s" % e, file=sys.stderr)
+            sys.exit(1)
+        labels, medoids = d_labels.cpu().numpy(), medoids.cpu().numpy()
+        t1 = time.perf_counter()
+        run = {"labels": labels, "values": None,
+               "stats": {"kmedoids": k, "kmedoids_medoids": [int(x) for x in medoids], "kmedoids_iterations": ks["iterations"],
+                         "kmedoids_converged": ks["converged"], "kmedoids_sizes": [int(x) for x in np.bincount(labels, minlength=k)],
+                         "kmedoids_ms": (t1 - t0) * 1e3, "kmedoids_inertia": ks["inertia"], "kmedoids_dtype": params.kmedoids_dtype,
+                         "kmedoids_phases_ms": {p: ks[p + "_ms"] for p in ("start", "rowsum", "assign", "update")}}}
+        mean = float("nan")
+        if scored:
+            try:
+                values, ss = ctx.silhouette(buf[:, :n], d_labels, k, want_stats=True)
+                run["values"] = values.cpu().numpy()
+                mean = ss["mean"]
+                run["stats"].update(silhouette_mean=mean, silhouette_cluster_means=silhouette_cluster_means(run["values"], labels, k),
+                                    silhouette_ms=(time.perf_counter() - t1) * 1e3, silhouette_passes=ss["passes"])
+            except api._lib.PhyloligoError as e:             # fewer than two clusters with a member: no silhouette
+                if sweep is None and params.silhouette is not None:
+                    print("Error, --silhouette: %s" % e, file=sys.stderr)
+                    sys.exit(1)
+                run["stats"].update(silhouette_mean=None, silhouette_cluster_means=None, silhouette_ms=None, silhouette_passes=None)
+        run["row"] = {"K": k, "iterations": ks["iterations"], "converged": ks["converged"], "empty_clusters": ks["empty_clusters"],
+                      "inertia": ks["inertia"], "silhouette_mean": mean, "sizes": run["stats"]["kmedoids_sizes"]}
+        runs.append(run)
+    if sweep is None:
+        best = runs[0]
+        LAST_KMEDOIDS = best["stats"]
+    else:
+        rows = [r["row"] for r in runs]
+        won = sweep_best(rows)
+        if won is None:
+            print("Error, --kmedoids-sweep %s: the mean silhouette of every K is NaN (the matrix holds undefined distances)"
+                  % params.kmedoids_sweep, file=sys.stderr)
+            sys.exit(1)
+        best = next(r for r in runs if r["row"] is won)
+        LAST_KMEDOIDS = dict(best["stats"], kmedoids_sweep=rows, kmedoids_sweep_best=won["K"])
     t_dist = time.perf_counter()
-    LAST_KMEDOIDS = {"kmedoids": k, "kmedoids_medoids": [int(x) for x in medoids], "kmedoids_iterations": ks["iterations"],
-                     "kmedoids_converged": ks["converged"], "kmedoids_sizes": [int(x) for x in np.bincount(labels, minlength=k)],
-                     "kmedoids_ms": (t_dist - t0) * 1e3, "kmedoids_inertia": ks["inertia"], "kmedoids_dtype": params.kmedoids_dtype,
-                     "kmedoids_phases_ms": {p: ks[p + "_ms"] for p in ("start", "rowsum", "assign", "update")}}
     _timing("single process: matrix + k-medoids %.3f s" % (t_dist - t_dist0))
     if params.out_freq_file:
         print("Writing frequency matrix")
         api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
     print("Writing cluster labels")
-    write_labels(params.out_file, labels)
+    write_labels(params.out_file, best["labels"])
+    if params.silhouette is not None:
+        write_silhouette(params.silhouette, best["values"])
+    if sweep is not None and params.sweep_out is not None:
+        write_sweep_table(params.sweep_out, [r["row"] for r in runs])
     if params.json_stats:
         _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
     return 0
@@ -983,7 +1110,8 @@ def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpu
              **({} if getattr(params, "knn", None) is None else
                 {"knn": params.knn, "knn_select_ms": None if LAST_STAGE2 is None else LAST_STAGE2.get("select_ms")}),
              **({} if getattr(params, "tsne", None) is None or LAST_TSNE is None else dict(LAST_TSNE, tsne_perplexity=params.tsne)),
-             **({} if getattr(params, "kmedoids", None) is None or LAST_KMEDOIDS is None else LAST_KMEDOIDS),
+             **({} if (getattr(params, "kmedoids", None) is None and getattr(params, "kmedoids_sweep", None) is None) or LAST_KMEDOIDS is None
+                else LAST_KMEDOIDS),
              **({} if not _clip_active(params) or LAST_CLIP is None else LAST_CLIP),
              "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
     with open(params.json_stats, "w") as fh:
