@@ -443,8 +443,8 @@ class Context:
                                 _np_ptr(y0), ctypes.byref(params), _np_ptr(y), ctypes.byref(res)))
         return (y, _tsne_stats(res, hist)) if want_stats else y
 
-    # ---- k-medoids on a distance matrix --------------------------------------------------------
-    def _kmed_matrix(self, matrix, square=True):
+    # ---- arguments of the calls that take a distance matrix (k-medoids, silhouettes, row medians) ----
+    def _matrix_arg(self, matrix, square=True):
         """(is_torch, matrix, dtype code, n, ld) of a 2-D float32 / float64 matrix with unit inner stride and row stride >= n;
         square=False: any [rows, n] (the row count is matrix.shape[0])"""
         if _is_torch(matrix):
@@ -468,6 +468,37 @@ class Context:
         ld = matrix.strides[0] // matrix.itemsize if rows > 1 else max(n, 1)
         return False, matrix, PO_F32 if matrix.dtype == np.float32 else PO_F64, n, ld
 
+    def _matrix_on_device(self, matrix, square=True):
+        import torch
+        is_t, matrix, code, n, ld = self._matrix_arg(matrix, square)
+        if not is_t:
+            matrix = torch.from_numpy(matrix).cuda(self.device)      # a strided view arrives with its row stride
+            ld = matrix.stride(0) if matrix.shape[0] > 1 else max(n, 1)
+        return is_t, matrix, code, n, ld
+
+    def _labels_on_device(self, labels, n, dev):
+        import torch
+        labels = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+        self._check_device(labels)
+        if labels.dtype != torch.int32 or labels.shape != (n,):
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels must be int32 [%d] (got %s %s)" % (n, labels.dtype, tuple(labels.shape)))
+        return labels.contiguous()
+
+    def _index_list_on_device(self, x, name, dev):
+        import torch
+        x = x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)
+        self._check_device(x)
+        if x.dtype != torch.int32 or x.dim() != 1:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "%s must be a 1-D int32 index list" % name)
+        return x.contiguous()
+
+    @staticmethod
+    def _check_n_clusters(n_clusters, n):
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= n:
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "n_clusters must be an integer in 1..n = %d (got %r)" % (n, n_clusters))
+        return int(n_clusters)
+
+    # ---- k-medoids on a distance matrix --------------------------------------------------------
     def kmedoids(self, matrix, n_clusters=8, max_iter=300, init="heuristic", want_stats=False):
         """k-medoids of a precomputed distance matrix [n, n] (float32 / float64, unit inner stride, any row stride >= n): what
         the reference's KMedoids(n_clusters, distance_metric="precomputed", max_iter=max_iter).fit(matrix) decides
@@ -477,12 +508,10 @@ class Context:
         empty_clusters, start_ms / rowsum_ms / assign_ms / update_ms).  numpy in -> numpy out (po_kmedoids: the matrix is
         copied to the device); torch CUDA tensor in -> tensors out on torch's current stream (po_kmedoids_dev).  With the
         heuristic start a row that sums to NaN is refused (PO_EINVAL); with explicit rows a NaN gives an unspecified result."""
-        is_t, matrix, code, n, ld = self._kmed_matrix(matrix)
-        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= n:
-            raise _lib.PhyloligoError(_lib.PO_EINVAL, "n_clusters must be an integer in 1..n = %d (got %r)" % (n, n_clusters))
+        is_t, matrix, code, n, ld = self._matrix_arg(matrix)
+        k = self._check_n_clusters(n_clusters, n)
         if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
             raise _lib.PhyloligoError(_lib.PO_EINVAL, "max_iter must be at least 1 (got %r)" % (max_iter,))
-        k = int(n_clusters)
         start = None
         if not (isinstance(init, str) and init == "heuristic"):
             if isinstance(init, str):
@@ -511,33 +540,17 @@ class Context:
                                      "assign_ms": res.assign_ms, "update_ms": res.update_ms}
         return labels, medoids
 
-    def _kmed_device(self, matrix, square=True):
-        import torch
-        is_t, matrix, code, n, ld = self._kmed_matrix(matrix, square)
-        if not is_t:
-            matrix = torch.from_numpy(matrix).cuda(self.device)      # a strided view arrives with its row stride
-            ld = matrix.stride(0) if matrix.shape[0] > 1 else max(n, 1)
-        return is_t, matrix, code, n, ld
-
     def kmedoids_costs(self, matrix, labels, rows=None):
         """float64 [n]: for every row i the sum of matrix[i, j] over the columns j with labels[j] == labels[i] - the candidate
         costs of one k-medoids update (po_kmedoids_costs_dev).  rows: only these rows, in this order; the bytes of a row's cost
         are the same either way.  numpy in -> numpy out; torch CUDA tensors in -> tensor out."""
         import torch
-        is_t, matrix, code, n, ld = self._kmed_device(matrix)
+        is_t, matrix, code, n, ld = self._matrix_on_device(matrix)
         dev = matrix.device
-        labels = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
-        self._check_device(labels)
-        if labels.dtype != torch.int32 or labels.shape != (n,):
-            raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels must be int32 [%d] (got %s %s)" % (n, labels.dtype, tuple(labels.shape)))
-        labels = labels.contiguous()
+        labels = self._labels_on_device(labels, n, dev)
         d_rows, count = None, n
         if rows is not None:
-            d_rows = rows if _is_torch(rows) else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-            self._check_device(d_rows)
-            if d_rows.dtype != torch.int32 or d_rows.dim() != 1:
-                raise _lib.PhyloligoError(_lib.PO_EINVAL, "rows must be a 1-D int32 index list")
-            d_rows = d_rows.contiguous()
+            d_rows = self._index_list_on_device(rows, "rows", dev)
             count = d_rows.numel()
         out = torch.empty((count,), dtype=torch.float64, device=dev)
         self._use_torch_stream()
@@ -550,13 +563,9 @@ class Context:
         """int32 [n]: labels[j] = argmin over c of matrix[medoids[c], j], the smaller c wins a tie (po_kmedoids_assign_dev).
         numpy in -> numpy out; torch CUDA tensors in -> tensor out."""
         import torch
-        is_t, matrix, code, n, ld = self._kmed_device(matrix)
+        is_t, matrix, code, n, ld = self._matrix_on_device(matrix)
         dev = matrix.device
-        medoids = medoids if _is_torch(medoids) else torch.from_numpy(np.ascontiguousarray(medoids, dtype=np.int32)).to(dev)
-        self._check_device(medoids)
-        if medoids.dtype != torch.int32 or medoids.dim() != 1:
-            raise _lib.PhyloligoError(_lib.PO_EINVAL, "medoids must be a 1-D int32 index list")
-        medoids = medoids.contiguous()
+        medoids = self._index_list_on_device(medoids, "medoids", dev)
         labels = torch.empty((n,), dtype=torch.int32, device=dev)
         self._use_torch_stream()
         check(self._lib.po_kmedoids_assign_dev(self._h, matrix.data_ptr(), code, n, ld, medoids.numel(), medoids.data_ptr(),
@@ -570,17 +579,7 @@ class Context:
             if labels.shape[0] == 0:
                 raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels are empty")
             n_clusters = int(labels.max()) + 1
-        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= int(n_clusters) <= n:
-            raise _lib.PhyloligoError(_lib.PO_EINVAL, "n_clusters must be an integer in 1..n = %d (got %r)" % (n, n_clusters))
-        return int(n_clusters)
-
-    def _sil_device_labels(self, labels, n, dev):
-        import torch
-        labels = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
-        self._check_device(labels)
-        if labels.dtype != torch.int32 or labels.shape != (n,):
-            raise _lib.PhyloligoError(_lib.PO_EINVAL, "labels must be int32 [%d] (got %s %s)" % (n, labels.dtype, tuple(labels.shape)))
-        return labels.contiguous()
+        return self._check_n_clusters(n_clusters, n)
 
     def cluster_sums(self, matrix, labels, n_clusters=None):
         """float64 [n, n_clusters]: S[i, c] = the sum of matrix[i, j] over the columns j with labels[j] == c, in float64 and in
@@ -588,8 +587,8 @@ class Context:
         column's bytes do not depend on n_clusters.  labels: int32 [n] in 0..n_clusters-1 (checked); n_clusters=None means
         max(labels) + 1.  Takes a torch CUDA tensor (numpy is copied to the device) and returns a torch CUDA tensor."""
         import torch
-        _, matrix, code, n, ld = self._kmed_device(matrix)
-        labels = self._sil_device_labels(labels, n, matrix.device)
+        _, matrix, code, n, ld = self._matrix_on_device(matrix)
+        labels = self._labels_on_device(labels, n, matrix.device)
         k = self._sil_clusters(labels, n, n_clusters)
         out = torch.empty((n, k), dtype=torch.float64, device=matrix.device)
         self._use_torch_stream()
@@ -604,12 +603,12 @@ class Context:
         than two non-empty clusters are refused.  numpy in -> numpy out (po_silhouette: the matrix is copied to the device);
         torch CUDA tensor in -> tensor out on torch's current stream (po_silhouette_dev).  want_stats: also a dict (mean,
         nonempty_clusters, passes = matrix reads made, sums_ms, finish_ms)."""
-        is_t, matrix, code, n, ld = self._kmed_matrix(matrix)
+        is_t, matrix, code, n, ld = self._matrix_arg(matrix)
         res = PoSilhouetteResult()
         rp = ctypes.byref(res) if want_stats else None
         if is_t:
             import torch
-            labels = self._sil_device_labels(labels, n, matrix.device)
+            labels = self._labels_on_device(labels, n, matrix.device)
             k = self._sil_clusters(labels, n, n_clusters)
             values = torch.empty((n,), dtype=torch.float64, device=matrix.device)
             self._use_torch_stream()
@@ -634,7 +633,7 @@ class Context:
         bin/phyloselect.R:339-357 (po_row_medians_dev).  A row that holds a NaN gives NaN.  numpy in -> numpy out (the matrix is
         copied to the device); torch CUDA tensor in -> tensor out on torch's current stream."""
         import torch
-        is_t, matrix, code, n, ld = self._kmed_device(matrix, square=False)
+        is_t, matrix, code, n, ld = self._matrix_on_device(matrix, square=False)
         rows = matrix.shape[0]
         out = torch.empty((rows,), dtype=torch.float64, device=matrix.device)
         self._use_torch_stream()

@@ -12,17 +12,11 @@
 //   update     medoid[c] <- that row if its cost is strictly below the current cost; a changed-flag for the host
 //
 // The row-sum kernel.  A row's sum depends on the row, the labels and n only - not on the launch, the rows that share a
-// workgroup, the leading dimension or the alignment of the row:
-//   - columns are cut into groups of V = 16 bytes / element size (4 float32, 2 float64); group g belongs to thread g mod 256
-//     of the row's workgroup, which walks its groups in ascending order and keeps one float64 accumulator per position
-//     inside the group (V independent chains); the last, partial group is just a short group;
-//   - a thread ends with ((a0 + a1) + (a2 + a3)), a wave with a fixed shuffle tree, the four waves with ((w0 + w1) + (w2 + w3));
-//   - rows on 16-byte boundaries (base and leading dimension) are read with one 16-byte load per group, any other layout
-//     with V element loads of the same group: same order, same bytes out;
-//   - excluded entries are replaced by +0 with a select, never multiplied, so a NaN outside the cluster stays outside.
+// workgroup, the leading dimension or the alignment of the row: it keeps the summation order written at the top of po_rows.h,
+// and takes every step of it from there.
 // A workgroup carries R rows (4 float32 / 2 float64: 0.8 MB of matrix per workgroup at 50 000 columns) through the same
 // groups, so the labels of a group - 4 bytes per column, from L2 - are loaded once for R rows of matrix from HBM.
-#include "po_internal.h"
+#include "po_rows.h"
 
 #include <algorithm>
 #include <vector>
@@ -30,29 +24,6 @@
 namespace {
 
 constexpr uint32_t kThreads = 256;
-constexpr uint64_t kNoKey = ~0ull;
-
-// float64 -> unsigned key with the same order (-0 = +0; NaN above +inf), as the k-NN selection orders its values
-__device__ inline uint64_t order_key(double v) {
-    if (v != v) return kNoKey - 1;
-    if (v == 0.0) v = 0.0;
-    const uint64_t b = static_cast<uint64_t>(__double_as_longlong(v));
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-template <typename T> struct vec16;
-template <> struct vec16<float> { using type = float4; };
-template <> struct vec16<double> { using type = double2; };
-template <int V> struct ivec;
-template <> struct ivec<4> { using type = int4; };
-template <> struct ivec<2> { using type = int2; };
-
-__device__ inline double wave_sum_fixed(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                                                              // lane 0 holds the sum
-}
-
 // pair p: row prow[p] (NULL: p), target ptgt[p] (NULL: labels[row]); MASKED = false: every column counts (labels unused)
 template <typename T, int R, bool ALIGNED, bool MASKED>
 __global__ __launch_bounds__(kThreads) void kmed_rowsum_kernel(const T* __restrict__ D, uint64_t ld, uint32_t n,
@@ -60,8 +31,6 @@ __global__ __launch_bounds__(kThreads) void kmed_rowsum_kernel(const T* __restri
                                                                const int32_t* __restrict__ labels, uint32_t npairs,
                                                                double* __restrict__ out) {
     constexpr uint32_t V = 16 / sizeof(T);
-    using vecT = typename vec16<T>::type;
-    using vecI = typename ivec<V>::type;
     __shared__ double wsum[R][kThreads / 64];
     const uint32_t tid = threadIdx.x;
     const uint32_t p0 = blockIdx.x * R;
@@ -84,25 +53,10 @@ __global__ __launch_bounds__(kThreads) void kmed_rowsum_kernel(const T* __restri
     for (uint32_t g = tid; g < full; g += kThreads) {
         const uint32_t j0 = g * V;
         int32_t lab[V];
-        if (MASKED) {
-            const vecI q = *reinterpret_cast<const vecI*>(labels + j0);     // the label array starts on a 16-byte boundary
-            const int32_t* qp = reinterpret_cast<const int32_t*>(&q);
-#pragma unroll
-            for (uint32_t u = 0; u < V; ++u) lab[u] = qp[u];
-        }
+        if (MASKED) po_load_labels<V>(labels, j0, lab);
         T v[R][V];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (ALIGNED) {
-                const vecT q = *reinterpret_cast<const vecT*>(s[r] + j0);
-                const T* qp = reinterpret_cast<const T*>(&q);
-#pragma unroll
-                for (uint32_t u = 0; u < V; ++u) v[r][u] = qp[u];
-            } else {
-#pragma unroll
-                for (uint32_t u = 0; u < V; ++u) v[r][u] = s[r][j0 + u];
-            }
-        }
+        for (int r = 0; r < R; ++r) po_load_group<T, ALIGNED>(s[r], j0, v[r]);
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -127,14 +81,11 @@ __global__ __launch_bounds__(kThreads) void kmed_rowsum_kernel(const T* __restri
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        double t;
-        if constexpr (V == 4) t = (acc[r][0] + acc[r][1]) + (acc[r][2] + acc[r][3]);
-        else t = acc[r][0] + acc[r][1];
-        t = wave_sum_fixed(t);
+        const double t = po_wave_sum_fixed(po_thread_tree(acc[r]));
         if ((tid & 63u) == 0) wsum[r][tid >> 6] = t;
     }
     __syncthreads();
-    if (tid < R && p0 + tid < npairs) out[p0 + tid] = (wsum[tid][0] + wsum[tid][1]) + (wsum[tid][2] + wsum[tid][3]);
+    if (tid < R && p0 + tid < npairs) out[p0 + tid] = po_block_tree(wsum[tid]);
 }
 
 // prow[0, n) = row index, ptgt[n, n + K) = cluster index: the fixed halves of the pair list
@@ -162,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void kmed_assign_kernel(const T* __restri
     labels[j] = arg;
 }
 
-// per cluster: the smallest key among its members' costs ...
+// per cluster: the smallest order-preserving key (po_order_key: -0 = +0, NaN above +inf) among its members' costs ...
 __global__ __launch_bounds__(kThreads) void kmed_best_kernel(const double* __restrict__ cost, const int32_t* __restrict__ labels, uint32_t n,
                                                              uint32_t K, unsigned long long* __restrict__ best) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -171,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void kmed_best_kernel(const double* __res
     if (c >= K) return;
     // the minimum only ever falls, so a key that does not beat what the word holds now (even a stale view of it) cannot
     // beat the final value either: most rows skip the atomic, which K words would otherwise serialise
-    const unsigned long long key = order_key(cost[i]);
+    const unsigned long long key = po_order_key(cost[i], false);
     if (key < *reinterpret_cast<volatile unsigned long long*>(&best[c])) atomicMin(&best[c], key);
 }
 
@@ -182,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void kmed_best_row_kernel(const double* _
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
     const uint32_t c = static_cast<uint32_t>(labels[i]);
-    if (c < K && best[c] == order_key(cost[i])) atomicMin(&best_row[c], i);
+    if (c < K && best[c] == po_order_key(cost[i], false)) atomicMin(&best_row[c], i);
 }
 
 // cost[n + c]: the current medoid's sum over the cluster.  An empty cluster (no row lowered best_row) keeps its medoid.
@@ -206,13 +157,12 @@ __global__ __launch_bounds__(kThreads) void kmed_check_range_kernel(const int32_
     if (i < count && (v[i] < 0 || static_cast<uint32_t>(v[i]) >= limit)) atomicMin(err, i);
 }
 
-// One workgroup: inertia = sum_j D[med[label[j]]][j] (per-thread strided partial sums, fixed tree) and the number of clusters
+// One workgroup: inertia = sum_j D[med[label[j]]][j] (per-thread strided partial sums, po_block1024_sum) and the number of clusters
 // without a member.  cnt [K] is zero on entry.
 template <typename T>
 __global__ __launch_bounds__(1024) void kmed_finish_kernel(const T* __restrict__ D, uint64_t ld, uint32_t n, const int32_t* __restrict__ med,
                                                            const int32_t* __restrict__ labels, uint32_t K, uint32_t* __restrict__ cnt,
                                                            double* __restrict__ inertia, uint32_t* __restrict__ n_empty) {
-    __shared__ double part[16];
     __shared__ uint32_t empties;
     const uint32_t tid = threadIdx.x;
     if (tid == 0) empties = 0;
@@ -222,18 +172,14 @@ __global__ __launch_bounds__(1024) void kmed_finish_kernel(const T* __restrict__
         acc += static_cast<double>(D[static_cast<uint64_t>(static_cast<uint32_t>(med[c])) * ld + j]);
         atomicAdd(&cnt[c], 1u);
     }
-    acc = wave_sum_fixed(acc);
-    if ((tid & 63u) == 0) part[tid >> 6] = acc;
     __threadfence();
-    __syncthreads();
+    const double total = po_block1024_sum(acc);                             // (its barrier also stands between the two uses of cnt)
     uint32_t mine = 0;
     for (uint32_t c = tid; c < K; c += 1024) mine += atomicAdd(&cnt[c], 0u) == 0 ? 1u : 0u;
     if (mine) atomicAdd(&empties, mine);
     __syncthreads();
     if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < 16; ++w) t += part[w];
-        *inertia = t;
+        *inertia = total;
         *n_empty = empties;
     }
 }
@@ -252,20 +198,15 @@ struct kmed_ws {
 };
 
 size_t kmed_ws_layout(uint64_t n, uint32_t K, uint8_t* base, kmed_ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t* p = base ? base + off : nullptr;
-        off += po_round_up(bytes, 256);
-        return p;
-    };
+    po_carver ws{base};
     const uint64_t m = n + K;
-    uint8_t* a = take(m * 4);
-    uint8_t* b = take(m * 4);
-    uint8_t* c = take(m * 8);
-    uint8_t* d = take((size_t)K * 8 + (size_t)K * 4);
-    uint8_t* e = take((size_t)K * 4);
-    uint8_t* f = take(16);
-    uint8_t* g = take(16);
+    uint8_t* a = ws.take(m * 4);
+    uint8_t* b = ws.take(m * 4);
+    uint8_t* c = ws.take(m * 8);
+    uint8_t* d = ws.take((size_t)K * 8 + (size_t)K * 4);
+    uint8_t* e = ws.take((size_t)K * 4);
+    uint8_t* f = ws.take(16);
+    uint8_t* g = ws.take(16);
     if (w) {
         w->prow = reinterpret_cast<int32_t*>(a);
         w->ptgt = reinterpret_cast<int32_t*>(b);
@@ -277,7 +218,7 @@ size_t kmed_ws_layout(uint64_t n, uint32_t K, uint8_t* base, kmed_ws* w) {
         w->scal = reinterpret_cast<double*>(g);
         w->fill_bytes = (size_t)K * 12;
     }
-    return off;
+    return ws.off;
 }
 
 int kmed_pinned(po_ctx* ctx) {
@@ -294,13 +235,11 @@ int kmed_workspace(po_ctx* ctx, uint64_t n, uint32_t K, kmed_ws* w) {
     return PO_OK;
 }
 
-bool rows_aligned(const void* d, uint64_t ld, size_t esz) { return (reinterpret_cast<uintptr_t>(d) & 15u) == 0 && (ld * esz) % 16 == 0; }
-
 template <typename T, int R>
 int launch_rowsum_t(po_ctx* ctx, const T* D, uint64_t ld, uint32_t n, const int32_t* prow, const int32_t* ptgt, const int32_t* labels,
                     uint32_t npairs, double* out) {
     const dim3 grid((npairs + R - 1) / R), block(kThreads);
-    const bool al = rows_aligned(D, ld, sizeof(T));
+    const bool al = po_rows_aligned(D, ld, sizeof(T));
     if (labels) {
         if (al) hipLaunchKernelGGL((kmed_rowsum_kernel<T, R, true, true>), grid, block, 0, ctx->stream, D, ld, n, prow, ptgt, labels, npairs, out);
         else hipLaunchKernelGGL((kmed_rowsum_kernel<T, R, false, true>), grid, block, 0, ctx->stream, D, ld, n, prow, ptgt, labels, npairs, out);
@@ -328,35 +267,22 @@ int launch_assign(po_ctx* ctx, const void* D, int f32, uint64_t ld, uint32_t n, 
     return PO_OK;
 }
 
-// device values v[count] all inside [0, limit)?  One synchronisation.  *bad: first offending position or 0xFFFFFFFF
-int check_range(po_ctx* ctx, const kmed_ws& w, const int32_t* v, uint32_t count, uint32_t limit, uint32_t* bad) {
-    uint32_t* h = reinterpret_cast<uint32_t*>(ctx->h_kmed);
-    PO_HIP(hipMemsetAsync(w.flag + 1, 0xFF, 4, ctx->stream));
-    hipLaunchKernelGGL(kmed_check_range_kernel, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, v, count, limit, w.flag + 1);
-    PO_CHECK_LAUNCH("kmed_check_range_kernel");
-    PO_HIP(hipMemcpyAsync(h, w.flag + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-    PO_HIP(hipStreamSynchronize(ctx->stream));
-    *bad = h[0];
-    return PO_OK;
-}
-
-int check_matrix_args(const char* who, po_ctx* ctx, const void* m, int dtype, uint64_t n, uint64_t ld) {
-    PO_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
-    PO_REQUIRE(dtype == PO_F64 || dtype == PO_F32, "%s: dtype must be PO_F64 or PO_F32 (got %d)", who, dtype);
-    PO_REQUIRE(n >= 1 && n < (1ull << 31), "%s: n = %llu outside 1 .. 2^31 - 1", who, (unsigned long long)n);
-    PO_REQUIRE(ld >= n, "%s: ld = %llu is smaller than n = %llu", who, (unsigned long long)ld, (unsigned long long)n);
-    PO_REQUIRE(m != nullptr, "%s: the matrix pointer is NULL", who);
-    const size_t esz = dtype == PO_F32 ? 4 : 8;
-    PO_REQUIRE((reinterpret_cast<uintptr_t>(m) % esz) == 0, "%s: the matrix pointer is not aligned to its element size", who);
-    return PO_OK;
-}
-
 }  // namespace
+
+int po_check_index_range(po_ctx* ctx, uint32_t* d_flag_word, uint32_t* h_word, const int32_t* v, uint32_t count, uint32_t limit, uint32_t* bad) {
+    PO_HIP(hipMemsetAsync(d_flag_word, 0xFF, 4, ctx->stream));
+    hipLaunchKernelGGL(kmed_check_range_kernel, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream, v, count, limit, d_flag_word);
+    PO_CHECK_LAUNCH("kmed_check_range_kernel");
+    PO_HIP(hipMemcpyAsync(h_word, d_flag_word, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PO_HIP(hipStreamSynchronize(ctx->stream));
+    *bad = *h_word;
+    return PO_OK;
+}
 
 extern "C" int po_kmedoids_costs_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, const int32_t* d_labels,
                                      const int32_t* d_rows, uint64_t n_rows, double* d_costs) {
     const char* who = "po_kmedoids_costs_dev";
-    int rc = check_matrix_args(who, ctx, d_matrix, dtype, n, ld);
+    int rc = po_check_matrix_args(who, ctx, d_matrix, dtype, n, ld);
     if (rc) return rc;
     PO_REQUIRE(d_labels != nullptr && d_costs != nullptr, "%s: NULL buffer", who);
     PO_REQUIRE(d_rows != nullptr || n_rows == 0 || n_rows == n, "%s: n_rows = %llu without a row list (pass 0 or n)", who,
@@ -369,7 +295,7 @@ extern "C" int po_kmedoids_costs_dev(po_ctx* ctx, const void* d_matrix, int dtyp
     const uint32_t count = d_rows ? (uint32_t)n_rows : (uint32_t)n;
     if (d_rows && count) {
         uint32_t bad = 0;
-        rc = check_range(ctx, w, d_rows, count, (uint32_t)n, &bad);
+        rc = po_check_index_range(ctx, w.flag + 1, reinterpret_cast<uint32_t*>(ctx->h_kmed), d_rows, count, (uint32_t)n, &bad);
         if (rc) return rc;
         PO_REQUIRE(bad == 0xFFFFFFFFu, "%s: rows[%u] is outside 0 .. n-1", who, bad);
     }
@@ -380,7 +306,7 @@ extern "C" int po_kmedoids_costs_dev(po_ctx* ctx, const void* d_matrix, int dtyp
 extern "C" int po_kmedoids_assign_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, uint32_t n_clusters,
                                       const int32_t* d_medoids, int32_t* d_labels) {
     const char* who = "po_kmedoids_assign_dev";
-    int rc = check_matrix_args(who, ctx, d_matrix, dtype, n, ld);
+    int rc = po_check_matrix_args(who, ctx, d_matrix, dtype, n, ld);
     if (rc) return rc;
     PO_REQUIRE(n_clusters >= 1 && n_clusters <= n, "%s: n_clusters = %u outside 1 .. n = %llu", who, n_clusters, (unsigned long long)n);
     PO_REQUIRE(d_medoids != nullptr && d_labels != nullptr, "%s: NULL buffer", who);
@@ -389,7 +315,7 @@ extern "C" int po_kmedoids_assign_dev(po_ctx* ctx, const void* d_matrix, int dty
     rc = kmed_workspace(ctx, n, n_clusters, &w);
     if (rc) return rc;
     uint32_t bad = 0;
-    rc = check_range(ctx, w, d_medoids, n_clusters, (uint32_t)n, &bad);
+    rc = po_check_index_range(ctx, w.flag + 1, reinterpret_cast<uint32_t*>(ctx->h_kmed), d_medoids, n_clusters, (uint32_t)n, &bad);
     if (rc) return rc;
     PO_REQUIRE(bad == 0xFFFFFFFFu, "%s: medoids[%u] is outside 0 .. n-1", who, bad);
     return launch_assign(ctx, d_matrix, dtype == PO_F32, ld, (uint32_t)n, d_medoids, n_clusters, d_labels);
@@ -400,7 +326,7 @@ extern "C" int po_kmedoids_dev(po_ctx* ctx, const void* d_matrix, int dtype, uin
                                po_kmedoids_result* result) {
     const char* who = "po_kmedoids_dev";
     if (result) memset(result, 0, sizeof(*result));
-    int rc = check_matrix_args(who, ctx, d_matrix, dtype, n, ld);
+    int rc = po_check_matrix_args(who, ctx, d_matrix, dtype, n, ld);
     if (rc) return rc;
     const uint32_t K = n_clusters, N = (uint32_t)n;
     PO_REQUIRE(K >= 1 && K <= n, "%s: n_clusters = %u outside 1 .. n = %llu", who, K, (unsigned long long)n);
@@ -525,27 +451,20 @@ extern "C" int po_kmedoids(po_ctx* ctx, const void* matrix, int dtype, uint64_t 
                            const int32_t* init_medoids, uint32_t max_iter, int32_t* labels, int32_t* medoids, po_kmedoids_result* result) {
     const char* who = "po_kmedoids";
     if (result) memset(result, 0, sizeof(*result));
-    int rc = check_matrix_args(who, ctx, matrix, dtype, n, ld);
+    int rc = po_check_matrix_args(who, ctx, matrix, dtype, n, ld);
     if (rc) return rc;
     PO_REQUIRE(n_clusters >= 1 && n_clusters <= n, "%s: n_clusters = %u outside 1 .. n = %llu", who, n_clusters, (unsigned long long)n);
     PO_REQUIRE(max_iter >= 1, "%s: max_iter must be at least 1", who);
     PO_REQUIRE(labels != nullptr && medoids != nullptr, "%s: NULL buffer", who);
     PO_HIP(hipSetDevice(ctx->device));
-    const size_t esz = dtype == PO_F32 ? 4 : 8;
-    const uint64_t ld_dev = po_round_up(n, 16 / esz);                       // device rows on 16-byte boundaries
-    const size_t b_mat = po_round_up(n * ld_dev * esz, 256), b_lab = po_round_up(n * 4, 256), b_med = po_round_up((size_t)n_clusters * 4, 256);
-    rc = po_buf_reserve(ctx, &ctx->ws_io, b_mat + b_lab + b_med);
-    if (rc == PO_ENOMEM) {
-        po_set_error("%s: the %llu x %llu %s matrix (%.1f GB) does not fit the device memory that is free%s", who, (unsigned long long)n,
-                     (unsigned long long)n, dtype == PO_F32 ? "float32" : "float64", (double)b_mat / 1e9,
-                     dtype == PO_F32 ? "" : "; a float32 matrix takes half");
-        return PO_ENOMEM;
-    }
+    const size_t b_lab = po_round_up(n * 4, 256), b_med = po_round_up((size_t)n_clusters * 4, 256);
+    void* base;
+    uint64_t ld_dev;
+    uint8_t* extra;
+    rc = po_stage_host_matrix(who, ctx, matrix, dtype, n, ld, b_lab + b_med, &base, &ld_dev, &extra);
     if (rc) return rc;
-    uint8_t* base = static_cast<uint8_t*>(ctx->ws_io.p);
-    int32_t* d_labels = reinterpret_cast<int32_t*>(base + b_mat);
-    int32_t* d_medoids = reinterpret_cast<int32_t*>(base + b_mat + b_lab);
-    PO_HIP(hipMemcpy2DAsync(base, ld_dev * esz, matrix, ld * esz, n * esz, n, hipMemcpyHostToDevice, ctx->stream));
+    int32_t* d_labels = reinterpret_cast<int32_t*>(extra);
+    int32_t* d_medoids = reinterpret_cast<int32_t*>(extra + b_lab);
     rc = po_kmedoids_dev(ctx, base, dtype, n, ld_dev, n_clusters, init_medoids, max_iter, d_labels, d_medoids, result);
     if (rc) return rc;
     PO_HIP(hipMemcpyAsync(labels, d_labels, n * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -20,7 +20,7 @@
 // LDS per workgroup: cap entries of (key 8 B, column 4 B, value 4 / 8 B), cap = 2 max(Kp, chunk), Kp = K rounded up to a power
 // of two, chunk = 256 threads x one 16-byte load (1 024 float32 / 512 float64 values).  At K = 1 024: 2 048 x 20 B = 40 KiB
 // (float64), 32 KiB (float32) - four workgroups fit the 160 KiB of a CU.
-#include "po_internal.h"
+#include "po_rows.h"
 
 namespace {
 
@@ -32,10 +32,6 @@ constexpr uint32_t kEmptyCol = 0xFFFFFFFFu;
 __device__ inline bool pair_less(uint64_t ka, uint32_t ca, uint64_t kb, uint32_t cb) {
     return ka < kb || (ka == kb && ca < cb);
 }
-
-template <typename T> struct vec16;
-template <> struct vec16<float> { using type = float4; };
-template <> struct vec16<double> { using type = double2; };
 
 // One batch: list rows row0 + blockIdx.x; candidate t of that row is src[blockIdx.x * ld + t], 0 <= t < len, at column
 // col0 + t, or at column cidx[blockIdx.x * ldc + t] when cidx is given (the merge: -1 = no candidate).  diag: column == row
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(int32_t* __restric
         const uint32_t e0 = c0 + tid * V;
         T v[V];
         if (aligned && e0 + V <= len) {
-            const typename vec16<T>::type q = *reinterpret_cast<const typename vec16<T>::type*>(s + e0);
+            const typename po_vec16<T>::type q = *reinterpret_cast<const typename po_vec16<T>::type*>(s + e0);
             const T* qp = reinterpret_cast<const T*>(&q);
 #pragma unroll
             for (uint32_t u = 0; u < V; ++u) v[u] = qp[u];

@@ -19,7 +19,7 @@
 // Histogram traffic: an LDS atomic per element would serialise on the few exponent bins a distance row occupies, so a wave first
 // peels its two most common digits (ballot of the lanes that share the first lane's digit, one add of the popcount) and only the
 // lanes left over add one by one.  LDS: 16 KiB histogram + 16 KiB candidates per workgroup, 5 workgroups (20 waves) per CU.
-#include "po_internal.h"
+#include "po_rows.h"
 
 namespace {
 
@@ -29,10 +29,6 @@ constexpr uint32_t kDigitBits = 12;
 constexpr uint32_t kBins = 1u << kDigitBits;
 constexpr uint32_t kCap = 2048;                 // candidates held in LDS
 constexpr uint32_t kUnroll = 4;                 // 16-byte loads in flight per thread
-
-template <typename T> struct vec16;
-template <> struct vec16<float> { using type = float4; };
-template <> struct vec16<double> { using type = double2; };
 
 __device__ inline double key_value(uint64_t k) {
     const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
@@ -49,7 +45,7 @@ __device__ inline uint32_t lane_rank(uint64_t m) {          // set bits of m bel
 template <typename T, bool ALIGNED, typename F>
 __device__ __forceinline__ void sweep_row(const T* __restrict__ s, uint32_t n, uint32_t tid, F&& f) {
     constexpr uint32_t V = 16 / sizeof(T);
-    using vecT = typename vec16<T>::type;
+    using vecT = typename po_vec16<T>::type;
     const uint32_t full = n / V, groups = (n + V - 1) / V;
     for (uint32_t g0 = 0; g0 < groups; g0 += kThreads * kUnroll) {
         T v[kUnroll][V];
@@ -275,12 +271,10 @@ __global__ __launch_bounds__(kThreads) void rowmed_kernel(const T* __restrict__ 
     }
 }
 
-bool rows_aligned(const void* d, uint64_t ld, size_t esz) { return (reinterpret_cast<uintptr_t>(d) & 15u) == 0 && (ld * esz) % 16 == 0; }
-
 template <typename T>
 int launch_rowmed(po_ctx* ctx, const T* D, uint64_t ld, uint32_t n, uint32_t rows, double* out, unsigned long long* passes) {
     const dim3 grid(rows), block(kThreads);
-    if (rows_aligned(D, ld, sizeof(T))) hipLaunchKernelGGL((rowmed_kernel<T, true>), grid, block, 0, ctx->stream, D, ld, n, out, passes);
+    if (po_rows_aligned(D, ld, sizeof(T))) hipLaunchKernelGGL((rowmed_kernel<T, true>), grid, block, 0, ctx->stream, D, ld, n, out, passes);
     else hipLaunchKernelGGL((rowmed_kernel<T, false>), grid, block, 0, ctx->stream, D, ld, n, out, passes);
     PO_CHECK_LAUNCH("rowmed_kernel");
     return PO_OK;

@@ -9,8 +9,7 @@
 //               S[i][c] / sizes[c] over the other non-empty clusters of the chunk                                n kChunk reads
 //   finish      s[i] from the two, and their mean: one workgroup, per-thread strided sums and a fixed tree
 //
-// The sums kernel keeps the summation order written at the top of po_kmedoids.hip, per cluster: 16-byte column groups, group g on
-// thread g mod 256, one float64 chain per position of the group, ((a0 + a1) + (a2 + a3)), the fixed wave tree, ((w0 + w1) + (w2 + w3)).
+// The sums kernel keeps the summation order written at the top of po_rows.h, per cluster, and takes every step of it from there.
 // An entry of another cluster is replaced by +0 with a select.  A cluster's chains see the same operands in the same order
 // whatever else the thread accumulates, so S[i][labels[i]] has the bytes po_kmedoids_costs_dev gives, and the bytes of S[i][c]
 // depend on the row, the labels and n alone: not on K, the chunk c falls in, the kernel variant, ld or the alignment.
@@ -21,7 +20,7 @@
 // workgroup R are chosen so that C x V x R <= 64 doubles = 128 VGPRs: float32 R = 4 / 2 / 1, float64 R = 4 / 4 / 2.  With the
 // group in flight (loaded while the current one is added) the compiler reports 108 - 192 VGPRs and no scratch (DESIGN.md has the
 // table): two or three waves per SIMD, each with its next 16-byte loads outstanding while it works through C x V x R selects and adds.
-#include "po_internal.h"
+#include "po_rows.h"
 
 #include <algorithm>
 
@@ -30,26 +29,11 @@ namespace {
 constexpr uint32_t kThreads = 256;
 constexpr uint32_t kChunk = PO_SILHOUETTE_CHUNK;
 
-template <typename T> struct vec16;
-template <> struct vec16<float> { using type = float4; };
-template <> struct vec16<double> { using type = double2; };
-template <int V> struct ivec;
-template <> struct ivec<4> { using type = int4; };
-template <> struct ivec<2> { using type = int2; };
-
-__device__ inline double wave_sum_fixed(double v) {                        // po_kmedoids.hip's tree
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;                                                              // lane 0 holds the sum
-}
-
 // out[i * out_ld + c] = S[i][c0 + c] for c < nc <= C and every row i < n.  labels starts on a 16-byte boundary.
 template <typename T, int C, int R, bool ALIGNED>
 __global__ __launch_bounds__(kThreads) void sil_sums_kernel(const T* __restrict__ D, uint64_t ld, uint32_t n, const int32_t* __restrict__ labels,
                                                             int32_t c0, uint32_t nc, double* __restrict__ out, uint64_t out_ld) {
     constexpr uint32_t V = 16 / sizeof(T);
-    using vecT = typename vec16<T>::type;
-    using vecI = typename ivec<V>::type;
     __shared__ double wsum[R][C][kThreads / 64];
     const uint32_t tid = threadIdx.x;
     const uint32_t i0 = blockIdx.x * R;
@@ -72,25 +56,13 @@ __global__ __launch_bounds__(kThreads) void sil_sums_kernel(const T* __restrict_
             T v[R][V];
         } cur, next;
         auto load = [&](uint32_t grp, group& dst) {
-            int32_t (&l)[V] = dst.lab;
-            T (&x)[R][V] = dst.v;
             const uint32_t j0 = grp * V;
-            const vecI q = *reinterpret_cast<const vecI*>(labels + j0);
-            const int32_t* qp = reinterpret_cast<const int32_t*>(&q);
+            int32_t l[V];
+            po_load_labels<V>(labels, j0, l);
 #pragma unroll
-            for (uint32_t u = 0; u < V; ++u) l[u] = qp[u] - c0;
+            for (uint32_t u = 0; u < V; ++u) dst.lab[u] = l[u] - c0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (ALIGNED) {
-                    const vecT w = *reinterpret_cast<const vecT*>(s[r] + j0);
-                    const T* wp = reinterpret_cast<const T*>(&w);
-#pragma unroll
-                    for (uint32_t u = 0; u < V; ++u) x[r][u] = wp[u];
-                } else {
-#pragma unroll
-                    for (uint32_t u = 0; u < V; ++u) x[r][u] = s[r][j0 + u];
-                }
-            }
+            for (int r = 0; r < R; ++r) po_load_group<T, ALIGNED>(s[r], j0, dst.v[r]);
         };
         load(g, cur);
         for (;;) {                                                          // the next group is on its way while this one is added
@@ -135,16 +107,13 @@ __global__ __launch_bounds__(kThreads) void sil_sums_kernel(const T* __restrict_
     for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            double t;
-            if constexpr (V == 4) t = (acc[r][c][0] + acc[r][c][1]) + (acc[r][c][2] + acc[r][c][3]);
-            else t = acc[r][c][0] + acc[r][c][1];
-            t = wave_sum_fixed(t);
+            const double t = po_wave_sum_fixed(po_thread_tree(acc[r][c]));
             if ((tid & 63u) == 0) wsum[r][c][tid >> 6] = t;
         }
     __syncthreads();
     if (tid < R * C) {
         const uint32_t r = tid / C, c = tid % C;
-        if (i0 + r < n && c < nc) out[static_cast<uint64_t>(i0 + r) * out_ld + c] = (wsum[r][c][0] + wsum[r][c][1]) + (wsum[r][c][2] + wsum[r][c][3]);
+        if (i0 + r < n && c < nc) out[static_cast<uint64_t>(i0 + r) * out_ld + c] = po_block_tree(wsum[r][c]);
     }
 }
 
@@ -193,11 +162,10 @@ __global__ __launch_bounds__(kThreads) void sil_fold_kernel(const double* __rest
     other[i] = b;
 }
 
-// One workgroup: s[i] of every row and mean = (sum of s) / n (per-thread strided partial sums, fixed tree).
+// One workgroup: s[i] of every row and mean = (sum of s) / n (per-thread strided partial sums, po_block1024_sum).
 __global__ __launch_bounds__(1024) void sil_finish_kernel(const double* __restrict__ own, const double* __restrict__ other,
                                                           const int32_t* __restrict__ labels, const uint32_t* __restrict__ sizes, uint32_t n,
                                                           double* __restrict__ values, double* __restrict__ mean) {
-    __shared__ double part[16];
     const uint32_t tid = threadIdx.x;
     double acc = 0.0;
     for (uint32_t i = tid; i < n; i += 1024) {
@@ -216,14 +184,8 @@ __global__ __launch_bounds__(1024) void sil_finish_kernel(const double* __restri
         values[i] = v;
         acc += v;
     }
-    acc = wave_sum_fixed(acc);
-    if ((tid & 63u) == 0) part[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < 16; ++w) t += part[w];
-        *mean = t / static_cast<double>(n);
-    }
+    const double total = po_block1024_sum(acc);
+    if (tid == 0) *mean = total / static_cast<double>(n);
 }
 
 // ---- workspace of one problem (ctx->ws_sil) -----------------------------------------------------------------------------------
@@ -238,19 +200,14 @@ struct sil_ws {
 };
 
 size_t sil_ws_layout(uint64_t n, uint32_t K, bool values, uint8_t* base, sil_ws* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t* p = base ? base + off : nullptr;
-        off += po_round_up(bytes, 256);
-        return p;
-    };
-    uint8_t* a = take(n * 4);
-    uint8_t* b = take((size_t)K * 4);
-    uint8_t* f = take(16);
-    uint8_t* g = take(16);
-    uint8_t* c = values ? take(n * kChunk * 8) : nullptr;
-    uint8_t* d = values ? take(n * 8) : nullptr;
-    uint8_t* e = values ? take(n * 8) : nullptr;
+    po_carver ws{base};
+    uint8_t* a = ws.take(n * 4);
+    uint8_t* b = ws.take((size_t)K * 4);
+    uint8_t* f = ws.take(16);
+    uint8_t* g = ws.take(16);
+    uint8_t* c = values ? ws.take(n * kChunk * 8) : nullptr;
+    uint8_t* d = values ? ws.take(n * 8) : nullptr;
+    uint8_t* e = values ? ws.take(n * 8) : nullptr;
     if (w) {
         w->labels = reinterpret_cast<int32_t*>(a);
         w->sizes = reinterpret_cast<uint32_t*>(b);
@@ -260,7 +217,7 @@ size_t sil_ws_layout(uint64_t n, uint32_t K, bool values, uint8_t* base, sil_ws*
         w->own = reinterpret_cast<double*>(d);
         w->other = reinterpret_cast<double*>(e);
     }
-    return off;
+    return ws.off;
 }
 
 int sil_workspace(po_ctx* ctx, uint64_t n, uint32_t K, bool values, sil_ws* w) {
@@ -274,7 +231,7 @@ int sil_workspace(po_ctx* ctx, uint64_t n, uint32_t K, bool values, sil_ws* w) {
 template <typename T, int C, int R>
 int launch_sums_t(po_ctx* ctx, const T* D, uint64_t ld, uint32_t n, const int32_t* labels, uint32_t c0, uint32_t nc, double* out, uint64_t out_ld) {
     const dim3 grid((n + R - 1) / R), block(kThreads);
-    const bool al = (reinterpret_cast<uintptr_t>(D) & 15u) == 0 && (ld * sizeof(T)) % 16 == 0;
+    const bool al = po_rows_aligned(D, ld, sizeof(T));
     if (al) hipLaunchKernelGGL((sil_sums_kernel<T, C, R, true>), grid, block, 0, ctx->stream, D, ld, n, labels, (int32_t)c0, nc, out, out_ld);
     else hipLaunchKernelGGL((sil_sums_kernel<T, C, R, false>), grid, block, 0, ctx->stream, D, ld, n, labels, (int32_t)c0, nc, out, out_ld);
     PO_CHECK_LAUNCH("sil_sums_kernel");
@@ -297,13 +254,8 @@ int launch_sums(po_ctx* ctx, const void* D, int f32, uint64_t ld, uint32_t n, co
 }
 
 int check_args(const char* who, po_ctx* ctx, const void* m, int dtype, uint64_t n, uint64_t ld, uint32_t K) {
-    PO_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
-    PO_REQUIRE(dtype == PO_F64 || dtype == PO_F32, "%s: dtype must be PO_F64 or PO_F32 (got %d)", who, dtype);
-    PO_REQUIRE(n >= 1 && n < (1ull << 31), "%s: n = %llu outside 1 .. 2^31 - 1", who, (unsigned long long)n);
-    PO_REQUIRE(ld >= n, "%s: ld = %llu is smaller than n = %llu", who, (unsigned long long)ld, (unsigned long long)n);
-    PO_REQUIRE(m != nullptr, "%s: the matrix pointer is NULL", who);
-    const size_t esz = dtype == PO_F32 ? 4 : 8;
-    PO_REQUIRE((reinterpret_cast<uintptr_t>(m) % esz) == 0, "%s: the matrix pointer is not aligned to its element size", who);
+    const int rc = po_check_matrix_args(who, ctx, m, dtype, n, ld);
+    if (rc) return rc;
     PO_REQUIRE(K >= 1 && K <= n, "%s: n_clusters = %u outside 1 .. n = %llu", who, K, (unsigned long long)n);
     return PO_OK;
 }
@@ -422,21 +374,14 @@ extern "C" int po_silhouette(po_ctx* ctx, const void* matrix, int dtype, uint64_
     if (rc) return rc;
     PO_REQUIRE(labels != nullptr && values != nullptr, "%s: NULL buffer", who);
     PO_HIP(hipSetDevice(ctx->device));
-    const size_t esz = dtype == PO_F32 ? 4 : 8;
-    const uint64_t ld_dev = po_round_up(n, 16 / esz);                       // device rows on 16-byte boundaries
-    const size_t b_mat = po_round_up(n * ld_dev * esz, 256), b_lab = po_round_up(n * 4, 256), b_val = po_round_up(n * 8, 256);
-    rc = po_buf_reserve(ctx, &ctx->ws_io, b_mat + b_lab + b_val);
-    if (rc == PO_ENOMEM) {
-        po_set_error("%s: the %llu x %llu %s matrix (%.1f GB) does not fit the device memory that is free%s", who, (unsigned long long)n,
-                     (unsigned long long)n, dtype == PO_F32 ? "float32" : "float64", (double)b_mat / 1e9,
-                     dtype == PO_F32 ? "" : "; a float32 matrix takes half");
-        return PO_ENOMEM;
-    }
+    const size_t b_lab = po_round_up(n * 4, 256), b_val = po_round_up(n * 8, 256);
+    void* base;
+    uint64_t ld_dev;
+    uint8_t* extra;
+    rc = po_stage_host_matrix(who, ctx, matrix, dtype, n, ld, b_lab + b_val, &base, &ld_dev, &extra);
     if (rc) return rc;
-    uint8_t* base = static_cast<uint8_t*>(ctx->ws_io.p);
-    int32_t* d_labels = reinterpret_cast<int32_t*>(base + b_mat);
-    double* d_values = reinterpret_cast<double*>(base + b_mat + b_lab);
-    PO_HIP(hipMemcpy2DAsync(base, ld_dev * esz, matrix, ld * esz, n * esz, n, hipMemcpyHostToDevice, ctx->stream));
+    int32_t* d_labels = reinterpret_cast<int32_t*>(extra);
+    double* d_values = reinterpret_cast<double*>(extra + b_lab);
     PO_HIP(hipMemcpyAsync(d_labels, labels, n * 4, hipMemcpyHostToDevice, ctx->stream));
     rc = po_silhouette_dev(ctx, base, dtype, n, ld_dev, d_labels, n_clusters, d_values, result);
     if (rc) return rc;

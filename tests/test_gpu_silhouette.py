@@ -124,6 +124,30 @@ def test_a_column_does_not_depend_on_the_cluster_count(ctx, torch):
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("n", [5, 257, 1027])
+def test_three_kernels_share_one_summation_order(ctx, torch, n, dtype):
+    """one cluster that holds every column: the silhouette sums kernel, the masked k-medoids row sums and the unmasked row sums
+    of the heuristic start add the same values, and csrc/po_rows.h gives all three their order - the same bytes.  The unmasked
+    sums are seen through the start they decide: with n_clusters = n every row is a medoid of a cluster of one (zero diagonal,
+    positive elsewhere), no update moves it, and the medoids are the rows in ascending order of their sums, ties to the
+    smaller row.  ld = n (element loads) and rows padded to 16 bytes (one load per group)."""
+    d = _rand_matrix(n, dtype, seed=n + 7)
+    zeros = torch.zeros(n, dtype=torch.int32, device="cuda")
+    padded = torch.zeros((n, (n + 3) // 4 * 4), dtype=torch.float32 if dtype == np.float32 else torch.float64, device="cuda")
+    padded[:, :n] = torch.from_numpy(d).cuda()
+    want = None
+    for t in (torch.from_numpy(d).cuda(), padded[:, :n]):
+        column = ctx.cluster_sums(t, zeros, 1).cpu().numpy()[:, 0]
+        np.testing.assert_allclose(column, d.astype(np.float64).sum(axis=1), rtol=COST_RTOL, atol=0.0)
+        assert _bytes(ctx.kmedoids_costs(t, zeros)) == column.tobytes()
+        labels, medoids = ctx.kmedoids(t, n_clusters=n, init="heuristic")
+        assert medoids.cpu().numpy().tolist() == np.argsort(column, kind="stable").tolist()
+        assert labels.cpu().numpy()[medoids.cpu().numpy()].tolist() == list(range(n))
+        want = column.tobytes() if want is None else want
+        assert column.tobytes() == want
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_results_do_not_depend_on_layout(ctx, torch, dtype):
     """n = 257 with ld = n; a view with ld = n + 3; a view one element into an aligned buffer; ld = 264 (every row on a 16-byte
     boundary): identical bytes of the sums and of the values"""
