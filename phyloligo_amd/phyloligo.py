@@ -18,7 +18,6 @@ from . import api
 from ._lib import METRICS, PO_KNN_MAX_K, STRANDS
 
 _ctx = None
-LAST_STAGE2 = None       # PoStats of the first stage-2 call of the last compute_distances() (what --json-stats reports)
 LAST_INGEST = None       # phase -> ms of the last compute_frequencies() when INGEST_PHASES is set (--json-stats, bench.py)
 INGEST_PHASES = False    # time every step of compute_frequencies() (synchronises the device between steps)
 
@@ -30,10 +29,11 @@ def _timing(text):
         sys.stderr.write("phyloligo_amd timing: %s\n" % text)
 
 
-def _context():
+def _context(device=None):
+    """the process's one context; the first call chooses its device (LOCAL_RANK unless a rank names its own)"""
     global _ctx
     if _ctx is None:
-        _ctx = api.Context(int(os.environ.get("LOCAL_RANK", "0")))
+        _ctx = api.Context(int(os.environ.get("LOCAL_RANK", "0")) if device is None else device)
     return _ctx
 
 
@@ -232,59 +232,19 @@ def _write_raw_f32(out_file, n, rows, writers=8, fix=None, base=None):
         os.close(fd)
 
 
-class _BlockWriter:
-    """Device blocks of one rank -> their byte ranges of the shared float32 container (the multi-GPU form of
-    _write_raw_f32): two pinned host buffers; the device-to-host copy of chunk k + 1 runs on a side stream while
-    po_pwrite_rows (parallel pwrite) puts chunk k into the file from a background thread."""
-
-    def __init__(self, fd, n, device, chunk_bytes=256 << 20, writers=8, base=0):
-        import concurrent.futures as cf
-        import torch
-        self.torch, self.fd, self.n, self.writers, self.base = torch, fd, n, writers, base
-        self.chunk = chunk_bytes
-        self.stage = [torch.empty(chunk_bytes // 4, dtype=torch.float32, pin_memory=True) for _ in range(2)]
-        self.pending = [None, None]
-        self.stream = torch.cuda.Stream(device)
-        self.pool = cf.ThreadPoolExecutor(max_workers=1)
-        self.k = 0
-
-    def put(self, t, row0, col0, fix=None):
-        """t[R, C] float32 on the device -> rows row0.., columns col0.. of the file"""
-        torch = self.torch
-        R, C = t.shape
-        if R == 0 or C == 0:
-            return
-        per = max(1, self.chunk // (C * 4))
-        self.stream.wait_stream(torch.cuda.current_stream(t.device))
-        for a in range(0, R, per):
-            b = min(R, a + per)
-            which = self.k & 1
-            self.k += 1
-            if self.pending[which] is not None:                  # the chunk written from this buffer two rounds ago
-                self.pending[which].result()
-            view = self.stage[which][:(b - a) * C].view(b - a, C)
-            with torch.cuda.stream(self.stream):
-                view.copy_(t[a:b], non_blocking=True)
-            self.stream.synchronize()                            # (the previous chunk is being written meanwhile)
-            host = view.numpy()
-            if fix is not None:
-                fix(host, row0 + a, row0 + b)
-            self.pending[which] = self.pool.submit(_pwrite_rows, self.fd, host, row0 + a, col0, self.n, self.writers, self.base)
-
-    def close(self):
-        try:
-            for f in self.pending:
-                if f is not None:
-                    f.result()
-        finally:
-            self.pool.shutdown(wait=True)
-
-
 _SINGLE_CALL_BYTES = 4 << 30      # larger float64 matrices are computed and copied in row blocks
 
 
 def _row_chunk(n, itemsize, budget=1 << 30):
     return max(128, (budget // max(1, n * itemsize)) // 128 * 128)
+
+
+def _hdf5_or_refuse(speak=True):
+    """the HDF5 writer, or exit 1 where this system has no libhdf5 for --large h5py"""
+    from . import hdf5
+    if not hdf5.available():
+        refuse("Error, --large h5py needs libhdf5 (>= 1.10), which was not found on this system", speak)
+    return hdf5
 
 
 def compute_distances(mthdrun, large, frequencies, freq_name, out_file, dist, threads_max=4, freqchunksize=250,
@@ -294,17 +254,19 @@ def compute_distances(mthdrun, large, frequencies, freq_name, out_file, dist, th
     compute_distances_memmap does (:394-427, container dtype :413) and returns None.
     `--large h5py`: writes the HDF5 file of compute_distances_h5py / join_distance_results (:456-534): one float32 dataset
     "distances" of shape (N, N), and returns None."""
+    return _distances(mthdrun, large, frequencies, out_file, dist)[0]
+
+
+def _distances(mthdrun, large, frequencies, out_file, dist):
+    """compute_distances() and, for --json-stats, the PoStats of its first stage-2 call: (result, stats or None)"""
     if mthdrun not in ("joblib", "scoop", "hip"):
         print("Error, method {} is not implemented for pairwise distances computation".format(mthdrun), file=sys.stderr)
-        return None
+        return None, None
     if dist not in METRICS:                                                  # :383-385
         print("Error, unknown metric methodfor joblib: {}".format(dist), file=sys.stderr)
         sys.exit(1)
     if large == "h5py" and mthdrun != "scoop":
-        from . import hdf5
-        if not hdf5.available():
-            print("Error, --large h5py needs libhdf5 (>= 1.10), which was not found on this system", file=sys.stderr)
-            sys.exit(1)
+        hdf5 = _hdf5_or_refuse()
     ctx = _context()
     counts = getattr(frequencies, "counts", None)
     totals = getattr(frequencies, "totals", None)
@@ -318,18 +280,16 @@ def compute_distances(mthdrun, large, frequencies, freq_name, out_file, dist, th
                                not np.array_equal(ctx.frequencies(counts, totals), np.asarray(frequencies))):
         counts = totals = None
 
-    global LAST_STAGE2
-    LAST_STAGE2 = None
+    first = []                               # the stats of the first stage-2 call
 
     def rows(lo, hi, dtype, symmetric, out=None):
-        global LAST_STAGE2
         if counts is not None:
             res, st = ctx.pairwise(counts, totals, dist, lo, hi, dtype=dtype, symmetric=symmetric, out=out, want_stats=True)
         else:
             res, st = ctx.pairwise_freq(np.asarray(frequencies, dtype=np.float64), dist, lo, hi, dtype=dtype,
                                         symmetric=symmetric, out=out, want_stats=True)
-        if LAST_STAGE2 is None:
-            LAST_STAGE2 = dict(st, rows=[int(lo), int(hi)])
+        if not first:
+            first.append(dict(st, rows=[int(lo), int(hi)]))
         return res
 
     if large in ("memmap", "h5py"):
@@ -344,15 +304,15 @@ def compute_distances(mthdrun, large, frequencies, freq_name, out_file, dist, th
             # matrix then goes into the dataset's contiguous data range exactly as it goes into the raw container
             base = hdf5.create_f32_dataset(out_file, "distances", n, n)
         _write_raw_f32(out_file, n, rows, fix=fix, base=base)
-        return None
+        return None, (first[0] if first else None)
     if n * n * 8 <= _SINGLE_CALL_BYTES:
-        return rows(0, n, "float64", True)
+        return rows(0, n, "float64", True), first[0]
     res = np.empty((n, n), dtype=np.float64)
     step = _row_chunk(n, 8)
     for lo in range(0, n, step):
         hi = min(n, lo + step)
         rows(lo, hi, "float64", False, out=res[lo:hi])          # straight into the result: no per-block ndarray
-    return res
+    return res, (first[0] if first else None)
 
 
 def get_cmd(argv=None):
@@ -443,11 +403,33 @@ def get_cmd(argv=None):
     return params
 
 
+# ---- refusals: the rules every mode shares, stated once --------------------------------------------------------------------------------
+# A mode is refused, in this order, by: its own checks of what it was combined with (`first`); --large, when it writes `writes` to
+# -o and no matrix container; -d KT, which is a correlation, `kt` saying why that matters to the mode; the checks of its own values
+# (`values`); more than one rank, `ranks` naming what would have to be spread over them; --method scoop.  A rule whose wording
+# the mode does not give does not apply to it.  `first` and `values` are iterables of reasons: the first one counts.
+def _first_reason(params, environ, who, first=(), writes=None, kt=None, values=(), ranks=None):
+    s = "" if " / " in who else "s"                      # "--clip-percentile / --min-size need", "--tsne needs"
+    for reason in first:
+        return reason
+    if writes is not None and params.large != "None":
+        return "Error, %s writes %s, not a matrix container: it cannot be combined with --large %s" % (who, writes, params.large)
+    if kt is not None and params.dist == "KT":
+        return "Error, %s need%s a distance: -d KT is a correlation (%s)" % (who, s, kt)
+    for reason in values:
+        return reason
+    if ranks is not None and (params.gpus > 1 or int(environ.get("WORLD_SIZE", "1")) > 1):
+        return "Error, %s run%s on one GPU: %s over several ranks (--gpus N > 1) is out of scope" % (who, s, ranks)
+    if params.mthdrun not in ("joblib", "hip"):
+        return "Error, %s support%s --method joblib|hip" % (who, s)
+    return None
+
+
 def _clip_active(params):
     return getattr(params, "clip_percentile", 1.0) != 1 or getattr(params, "min_size", 0) != 0
 
 
-def _clip_refused(params):
+def _clip_refused(params, environ=os.environ):
     """the reason --clip-percentile / --min-size cannot run with these options, or None"""
     p, size = getattr(params, "clip_percentile", 1.0), getattr(params, "min_size", 0)
     if not 0.0 <= p <= 1.0:
@@ -458,48 +440,39 @@ def _clip_refused(params):
         if getattr(params, "clip_out", None) is not None:
             return "Error, --clip-out lists the contigs a filter keeps: give --clip-percentile P < 1 or --min-size L > 0 with it"
         return None
-    if params.dist == "KT":
-        return "Error, --clip-percentile / --min-size need a distance: -d KT is a correlation (a large median does not mean distant)"
-    if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "Error, --clip-percentile / --min-size run on one GPU: a clip over several ranks (--gpus N > 1) is out of scope"
-    if params.mthdrun not in ("joblib", "hip"):
-        return "Error, --clip-percentile / --min-size support --method joblib|hip"
-    return None
+    return _first_reason(params, environ, "--clip-percentile / --min-size", kt="a large median does not mean distant", ranks="a clip")
 
 
-def _knn_refused(params):
+def _knn_refused(params, environ=os.environ):
     """the reason --knn cannot run with these options, or None"""
     if params.knn is None:
         return None
-    if not 1 <= params.knn <= PO_KNN_MAX_K:
-        return "Error, --knn K needs 1 <= K <= %d (got %d)" % (PO_KNN_MAX_K, params.knn)
-    if params.large != "None":
-        return "Error, --knn writes a neighbour graph, not a matrix container: it cannot be combined with --large %s" % params.large
-    if params.mthdrun not in ("joblib", "hip"):
-        return "Error, --knn supports --method joblib|hip"
-    return None
+
+    def first():
+        if not 1 <= params.knn <= PO_KNN_MAX_K:
+            yield "Error, --knn K needs 1 <= K <= %d (got %d)" % (PO_KNN_MAX_K, params.knn)
+
+    return _first_reason(params, environ, "--knn", first(), writes="a neighbour graph")
 
 
-def _tsne_refused(params):
+def _tsne_refused(params, environ=os.environ):
     """the reason --tsne cannot run with these options, or None"""
     if getattr(params, "tsne", None) is None:
         return None
-    if params.knn is not None:
-        return "Error, --tsne writes an embedding and --knn a neighbour graph to -o: give one of them"
-    if params.large != "None":
-        return "Error, --tsne writes n x 2 coordinates as text, not a matrix container: it cannot be combined with --large %s" % params.large
-    if params.dist == "KT":
-        return "Error, --tsne needs a distance: -d KT is a correlation (its neighbour lists are ordered descending)"
-    if not params.tsne >= 1.0 or int(3.0 * params.tsne + 1) > PO_KNN_MAX_K:
-        return ("Error, --tsne PERPLEXITY needs 1 <= PERPLEXITY and int(3 * PERPLEXITY + 1) <= %d neighbours, i.e. at most %d (got %g)"
-                % (PO_KNN_MAX_K, (PO_KNN_MAX_K - 1) // 3, params.tsne))
-    if params.tsne_iter < 1:
-        return "Error, --tsne-iter needs at least 1 iteration (got %d)" % params.tsne_iter
-    if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "Error, --tsne runs on one GPU: an embedding over several ranks (--gpus N > 1) is out of scope"
-    if params.mthdrun not in ("joblib", "hip"):
-        return "Error, --tsne supports --method joblib|hip"
-    return None
+
+    def first():
+        if params.knn is not None:
+            yield "Error, --tsne writes an embedding and --knn a neighbour graph to -o: give one of them"
+
+    def values():
+        if not params.tsne >= 1.0 or int(3.0 * params.tsne + 1) > PO_KNN_MAX_K:
+            yield ("Error, --tsne PERPLEXITY needs 1 <= PERPLEXITY and int(3 * PERPLEXITY + 1) <= %d neighbours, i.e. at most %d (got %g)"
+                   % (PO_KNN_MAX_K, (PO_KNN_MAX_K - 1) // 3, params.tsne))
+        if params.tsne_iter < 1:
+            yield "Error, --tsne-iter needs at least 1 iteration (got %d)" % params.tsne_iter
+
+    return _first_reason(params, environ, "--tsne", first(), writes="n x 2 coordinates as text",
+                         kt="its neighbour lists are ordered descending", values=values(), ranks="an embedding")
 
 
 def parse_sweep(text):
@@ -522,7 +495,7 @@ def _sweep_range(params):
     return None if text is None else parse_sweep(text)
 
 
-def _kmedoids_refused(params):
+def _kmedoids_refused(params, environ=os.environ):
     """the reason --kmedoids / --kmedoids-sweep (and --silhouette, --sweep-out with them) cannot run with these options, or None"""
     sweep = getattr(params, "kmedoids_sweep", None)
     if getattr(params, "sweep_out", None) is not None and sweep is None:
@@ -532,310 +505,104 @@ def _kmedoids_refused(params):
             return "Error, --silhouette scores a clustering: give --kmedoids K or --kmedoids-sweep LO:HI with it"
         return None
     who = "--kmedoids" if sweep is None else "--kmedoids-sweep"
-    if sweep is not None:
-        if params.kmedoids is not None:
-            return "Error, --kmedoids-sweep tries every K of its range: it cannot be combined with --kmedoids %d" % params.kmedoids
-        try:
-            parse_sweep(sweep)
-        except ValueError as e:
-            return "Error, %s" % e
-    if params.knn is not None or getattr(params, "tsne", None) is not None:
-        return ("Error, %s writes cluster labels to -o, --knn a neighbour graph and --tsne an embedding: give one of them" % who)
-    if params.large != "None":
-        return "Error, %s writes one label per contig as text, not a matrix container: it cannot be combined with --large %s" % (who, params.large)
-    if params.dist == "KT":
-        return "Error, %s needs a distance: -d KT is a correlation (larger means closer)" % who
-    if sweep is None and params.kmedoids < 1:
-        return "Error, --kmedoids K needs 1 <= K <= number of contigs (got %d)" % params.kmedoids
-    if params.kmedoids_iter < 1:
-        return "Error, --kmedoids-iter needs at least 1 iteration (got %d)" % params.kmedoids_iter
-    if params.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "Error, %s runs on one GPU: clustering over several ranks (--gpus N > 1) is out of scope" % who
-    if params.mthdrun not in ("joblib", "hip"):
-        return "Error, %s supports --method joblib|hip" % who
+
+    def first():
+        if sweep is not None:
+            if params.kmedoids is not None:
+                yield "Error, --kmedoids-sweep tries every K of its range: it cannot be combined with --kmedoids %d" % params.kmedoids
+            try:
+                parse_sweep(sweep)
+            except ValueError as e:
+                yield "Error, %s" % e
+        if params.knn is not None or getattr(params, "tsne", None) is not None:
+            yield "Error, %s writes cluster labels to -o, --knn a neighbour graph and --tsne an embedding: give one of them" % who
+
+    def values():
+        if sweep is None and params.kmedoids < 1:
+            yield "Error, --kmedoids K needs 1 <= K <= number of contigs (got %d)" % params.kmedoids
+        if params.kmedoids_iter < 1:
+            yield "Error, --kmedoids-iter needs at least 1 iteration (got %d)" % params.kmedoids_iter
+
+    return _first_reason(params, environ, who, first(), writes="one label per contig as text", kt="larger means closer",
+                         values=values(), ranks="clustering")
+
+
+def refusal(params, environ=os.environ):
+    """the first reason this command line cannot run, or None; a new mode adds its function here, where main() is to ask it"""
+    for refused in (_clip_refused, _kmedoids_refused, _tsne_refused, _knn_refused):
+        reason = refused(params, environ)
+        if reason:
+            return reason
     return None
+
+
+def refuse(reason, speak=True):
+    """exit 1 when there is a reason; one process says it on stderr (of several ranks: rank 0)"""
+    if reason:
+        if speak:
+            print(reason, file=sys.stderr)
+        sys.exit(1)
+
+
+def launch_plan(params, environ):
+    """What `python -m phyloligo_amd` decides before anything touches torch or the library: (the reason to refuse or None,
+    the GPUs asked for, whether torch has to be loaded before the library).  torch comes first exactly where the run keeps the
+    matrix in a torch tensor (k-medoids, the sweep, an active clip) or is one of several ranks: it bundles its own HIP runtime, and
+    a process must hold exactly one (_lib.PREFER_NO_TORCH)."""
+    needs_torch = (int(environ.get("WORLD_SIZE", "1")) > 1 or params.kmedoids is not None or params.kmedoids_sweep is not None or
+                   _clip_active(params))
+    return refusal(params, environ), params.gpus, needs_torch
+
+
+# ---- the modes: what a run computes from the profiles and writes to -o -----------------------------------------------------------------
+# A mode is a function (params, frequencies) -> (PO_CLI_TIMING label, the line printed before writing or None, the function that
+# writes its output, the stats of its first stage-2 call, its own --json-stats keys).  main() owns everything around it.
+def _write_freq(params, frequencies, speak=True):
+    """-q: the frequency matrix as text, before the run's own output (frequencies: a function, called only when it is wanted)"""
+    if params.out_freq_file and speak:
+        print("Writing frequency matrix")
+        api.write_mat_text(params.out_freq_file, frequencies())
+
+
+def _matrix_mode(params, frequencies):
+    """the N x N matrix: returned and written as text, or written into its container by compute_distances itself"""
+    res, stage2 = _distances(params.mthdrun, params.large, frequencies, params.out_file, params.dist)
+    text = not (params.mthdrun in ("joblib", "hip") and params.large != "None")          # :1064
+    return ("distances%s" % (" + container" if params.large in ("memmap", "h5py") else ""), "Writing distance matrix" if text else None,
+            lambda: api.write_mat_text(params.out_file, res), stage2, {})
+
+
+def _knn_mode(params, frequencies):
+    """--knn in one process: the graph from the integer profiles (po_knn, float64), written to -o"""
+    counts, n = frequencies.counts, frequencies.shape[0]
+    idx, val, st = _context().knn(counts, frequencies.totals, params.knn, params.dist, "float64", want_stats=True)
+    return ("k-NN graph", "Writing distance matrix", lambda: _write_knn(params, counts, idx, val), dict(st, rows=[0, n]),
+            {"knn": params.knn, "knn_select_ms": st.get("select_ms")})
 
 
 def _write_knn(params, counts, idx, val):
     api.write_knn_npz(params.out_file, idx, val, api.knn_self_values(params.dist, val, counts=counts))
 
 
-def main_distributed(params):
-    """The same job on the GPUs of one node, one process per GPU (launched by torch.distributed.run: WORLD_SIZE > 1).
-
-    The reference spreads row slices over joblib workers that all see the frequency matrix (gen_even_slices,
-    phyloligo.py:424,516).  Here every rank profiles its own block of contigs, ONE all-gather moves the exact count
-    matrix, the block grid is dealt out like a round-robin tournament (dist.RowBlockPlan: every unordered pair evaluated
-    once in the whole job), the transposed blocks go to the ranks whose rows they complete, and every rank writes its
-    rows of the output: straight into its byte range of the float32 container (--large memmap), or in rank order into the
-    text matrix.  PO_CLI_REHEARSAL=1: all ranks on GPU 0 with gloo collectives (a one-GPU box can run the code path)."""
-    import torch
-    import torch.distributed as tdist
-    from .dist import RowBlockPlan
-    t_start = time.perf_counter()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    rehearsal = os.environ.get("PO_CLI_REHEARSAL") == "1"
-    local = 0 if rehearsal else int(os.environ.get("LOCAL_RANK", "0"))
-    if params.mthdrun not in ("joblib", "hip"):
-        if rank == 0:
-            print("Error, the multi-GPU run supports --method joblib|hip", file=sys.stderr)
-        sys.exit(1)
-    if params.large == "h5py":
-        from . import hdf5
-        if not hdf5.available():
-            if rank == 0:
-                print("Error, --large h5py needs libhdf5 (>= 1.10), which was not found on this system", file=sys.stderr)
-            sys.exit(1)
-    if params.strand not in STRANDS or params.dist not in METRICS:
-        sys.exit(1)
-    for refused in (_clip_refused(params), _kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
-        if refused:
-            if rank == 0:
-                print(refused, file=sys.stderr)
-            sys.exit(1)
-    from .dist import first_contact
-    first_contact("cuda.set_device", torch.cuda.set_device, local)
-    if rehearsal:
-        first_contact("init_process_group", tdist.init_process_group, "gloo")
-    else:
-        first_contact("init_process_group", tdist.init_process_group, "nccl", device_id=torch.device("cuda", local))
-    global _ctx
-    _ctx = api.Context(local)
-    ctx, dev = _ctx, torch.device("cuda", local)
-    say = print if rank == 0 else (lambda *a, **k: None)
-    say("Using pattern {}".format(params.pattern))
-    if rank == 0 and not os.path.isdir(params.workdir):
-        os.makedirs(params.workdir)
-    say("Computing frequencies")
-    ingest = read_fasta_device(params.genome)
-    if ingest is not None:
-        d_seq, d_off, _ = ingest
-    else:
-        seq, offsets, _ = read_fasta(params.genome)
-        d_seq, d_off = torch.from_numpy(seq).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    n = int(d_off.numel()) - 1
-    plan = RowBlockPlan(n, world)
-    lo, hi = plan.rows(rank)
-    my_off = (d_off[lo:hi + 1] - d_off[lo]).contiguous()
-    my_seq = d_seq[int(d_off[lo]):int(d_off[hi])]
-    if my_seq.data_ptr() % 16:                                  # the kernels read aligned 16-byte vectors
-        my_seq = my_seq.clone()
-    my_counts, my_totals = ctx.count_profiles(my_seq, my_off, params.pattern, params.strand)
-    if rehearsal:
-        counts, totals = first_contact("all_gather_profiles", plan.all_gather_profiles, my_counts.cpu(), my_totals.cpu(), tdist)
-        counts, totals = counts.to(dev), totals.to(dev)
-    else:
-        def gather():                     # the ranks' first collective: a failure surfaces at the synchronize at the latest
-            c, t = plan.all_gather_profiles(my_counts, my_totals, tdist)
-            torch.cuda.synchronize(dev)
-            return c, t
-        counts, totals = first_contact("all_gather_profiles", gather)
-    say("Computing Pairwise distances")
-    t_dist0 = time.perf_counter()
-    if params.knn is not None:
-        return _knn_distributed(params, ctx, plan, rank, world, counts, totals, rehearsal, tdist, t_start, t_dist0)
-    dtype = torch.float32 if params.large in ("memmap", "h5py") else torch.float64
-    slab, mirrors = plan.allocate(rank, dev, dtype)
-    plan.compute(ctx, counts, totals, params.dist, rank, slab, mirrors)
-    torch.cuda.synchronize(dev)
-    t_computed = time.perf_counter()
-    if params.large in ("memmap", "h5py"):
-        # The row-completing exchange runs first (point to point over xGMI: cheap next to any file system), so that every
-        # rank holds ITS ROWS of the matrix whole and writes one contiguous byte range of the file in large pieces.  Measured
-        # on the gpurun box (tools/ubench/container_write_modes.cpp, page cache of overlay/ext4, 3.6 GB): buffered writes
-        # take the inode lock, so ranks that each pwrite their 60 kB pieces of every row reach 4.7 GB/s between two of them and
-        # 2.5 GB/s between eight (the lock changes hands at every call; round 3 did exactly that, 0.82 s for this file),
-        # a shared mapping written with memcpy 0.6 - 2.7 GB/s, while contiguous row slabs in large pieces reach 11 GB/s from
-        # two and 15.6 GB/s from eight processes.
-        if params.out_freq_file and rank == 0:
-            print("Writing frequency matrix")
-            api.write_mat_text(params.out_freq_file, ctx.frequencies(counts, totals).cpu().numpy())
-        base = [0]
-        if rank == 0:
-            if params.large == "h5py":                          # libhdf5 creates and sizes the file; the ranks fill the dataset's data range
-                base[0] = hdf5.create_f32_dataset(params.out_file, "distances", n, n)
-            else:
-                os.close(_open_raw_container(params.out_file, n * n * 4))
-        tdist.broadcast_object_list(base, src=0)                # where the matrix starts in the file
-        empty = (totals.cpu().numpy() == 0) if params.dist == "BC" else None
-
-        def diag_fix(host, a, b):                               # rows [a, b) of the matrix, whole
-            _bc_memmap_diagonal(host, a, b, np.flatnonzero(empty[a:b]) + a)
-
-        fix = diag_fix if (empty is not None and empty[lo:hi].any()) else None
-        if rehearsal:                                           # gloo moves host tensors; the slab stays on the device
-            mirrors_h = [None if m is None else m.cpu() for m in mirrors]
-            del mirrors
-            plan.complete_rows(rank, slab, mirrors_h, tdist, stage_device="cpu")
-            del mirrors_h
-        else:
-            plan.complete_rows(rank, slab, mirrors, tdist)
-            del mirrors
-        torch.cuda.synchronize(dev)
-        t_exchanged = time.perf_counter()
-        tdist.barrier()                                         # the file exists and has its size
-        fd = os.open(params.out_file, os.O_RDWR)
-        # (two pinned chunks of at most 256 MB; pinning costs ~0.07 s per GB, a small job does not pay for more than its slab)
-        writer = _BlockWriter(fd, n, dev, chunk_bytes=min(256 << 20, max(1 << 20, (hi - lo) * n * 4)), base=int(base[0]))
-        try:
-            writer.put(slab, lo, 0, fix=fix)                    # device -> pinned host chunks -> parallel pwrite, overlapped
-        finally:
-            try:
-                writer.close()
-            finally:
-                os.close(fd)
-        tdist.barrier()
-        t_end = time.perf_counter()
-        _timing("rank %d of %d: distances + container %.3f s (allocate + compute %.3f, row-completing exchange %.3f, copy + write %.3f)"
-                % (rank, world, t_end - t_dist0, t_computed - t_dist0, t_exchanged - t_computed, t_end - t_exchanged))
-        if params.json_stats and rank == 0:
-            _write_json_stats(params, _Shape(n, int(counts.shape[1])), t_dist0 - t_start, t_end - t_dist0, 0.0, t_end - t_start, gpus=world)
-        tdist.destroy_process_group()
-        return 0
-    # text matrix: rows have to be complete - the transposed blocks go to the ranks whose rows they belong to
-    if rehearsal:                                               # gloo moves host tensors
-        slab_h, mirrors_h = slab.cpu(), [None if m is None else m.cpu() for m in mirrors]
-        del slab, mirrors
-        slab = plan.complete_rows(rank, slab_h, mirrors_h, tdist)
-    else:
-        plan.complete_rows(rank, slab, mirrors, tdist)
-        torch.cuda.synchronize(dev)
-        del mirrors
-    step = max(1, (256 << 20) // max(1, n * slab.element_size()))     # rows per host copy: the slab never sits on the host whole
-
-    def row_chunks():
-        for a in range(0, hi - lo, step):
-            yield a, slab[a:min(hi - lo, a + step)].cpu().numpy()
-
-    if params.out_freq_file and rank == 0:
-        print("Writing frequency matrix")
-        api.write_mat_text(params.out_freq_file, ctx.frequencies(counts, totals).cpu().numpy())
-    say("Writing distance matrix")
-    for r in range(world):                                      # rank order = row order
-        if r == rank:
-            if r == 0 and hi == lo:
-                api.write_mat_text(params.out_file, np.zeros((0, n)))
-            for a, rows in row_chunks():
-                api.write_mat_text(params.out_file, rows, append=(r > 0 or a > 0))
-        tdist.barrier()
-    if params.json_stats and rank == 0:
-        t_end = time.perf_counter()
-        _write_json_stats(params, _Shape(n, int(counts.shape[1])), t_dist0 - t_start, t_computed - t_dist0, t_end - t_computed,
-                          t_end - t_start, gpus=world)
-    tdist.destroy_process_group()
-    return 0
-
-
-def _knn_distributed(params, ctx, plan, rank, world, counts, totals, rehearsal, tdist, t_start, t_dist0):
-    """--knn on several GPUs: every rank selects from the blocks of its tournament work list (partial lists over all n rows),
-    rank 0 gathers the lists, merges them and writes the graph.  No row-completing exchange: the lists are [n, K], not rows."""
-    import torch
-    global LAST_STAGE2
-    n = int(counts.shape[0])
-    idx, val, st = ctx.knn_blocks(counts, totals, params.knn, plan.work(rank), params.dist, "float64", want_stats=True)
-    torch.cuda.synchronize()
-    t_computed = time.perf_counter()
-    if rehearsal:                                               # gloo moves host tensors
-        idx, val = idx.cpu(), val.cpu()
-    idx_all = [torch.empty_like(idx) for _ in range(world)]
-    val_all = [torch.empty_like(val) for _ in range(world)]
-    tdist.all_gather(idx_all, idx)
-    tdist.all_gather(val_all, val)
-    if params.out_freq_file and rank == 0:
-        print("Writing frequency matrix")
-        api.write_mat_text(params.out_freq_file, ctx.frequencies(counts, totals).cpu().numpy())
-    if rank == 0:
-        print("Writing distance matrix")
-        dev = counts.device
-        m_idx, m_val = ctx.knn_merge(torch.stack(idx_all).to(dev), torch.stack(val_all).to(dev), params.dist)
-        _write_knn(params, counts.cpu().numpy(), m_idx.cpu().numpy(), m_val.cpu().numpy())
-        LAST_STAGE2 = dict(st, rows=[0, n])
-        if params.json_stats:
-            t_end = time.perf_counter()
-            _write_json_stats(params, _Shape(n, int(counts.shape[1])), t_dist0 - t_start, t_computed - t_dist0, t_end - t_computed,
-                              t_end - t_start, gpus=world)
-    tdist.barrier()
-    tdist.destroy_process_group()
-    return 0
-
-
-def main(argv=None):
-    params = get_cmd(argv)
-    if type(params.pattern) == int:                      # :1040-1041
-        params.pattern = str("1") * params.pattern
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return main_distributed(params)
-    for refused in (_clip_refused(params), _kmedoids_refused(params), _tsne_refused(params), _knn_refused(params)):
-        if refused:
-            print(refused, file=sys.stderr)
-            sys.exit(1)
-    t_start = time.perf_counter()
-    print("Using pattern {}".format(params.pattern))
-    if not os.path.isdir(params.workdir):
-        os.makedirs(params.workdir)
-    print("Computing frequencies")
-    global INGEST_PHASES
-    INGEST_PHASES = bool(params.json_stats)              # the phase times of the ingest go into the JSON record
-    frequencies, freq_name = compute_frequencies(params.mthdrun, params.large, params.genome, params.pattern,
-                                                 params.strand, params.distchunksize, params.threads_max,
-                                                 params.workdir)
-    t_freq = time.perf_counter()
-    if _clip_active(params):
-        frequencies = _clip(params, frequencies)
-    print("Computing Pairwise distances")
-    t_dist0 = time.perf_counter()
-    if params.kmedoids is not None or params.kmedoids_sweep is not None:
-        return _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0)
-    if params.tsne is not None:
-        return _tsne_single(params, frequencies, t_start, t_freq, t_dist0)
-    if params.knn is not None:
-        return _knn_single(params, frequencies, t_start, t_freq, t_dist0)
-    res = compute_distances(params.mthdrun, params.large, frequencies, freq_name, params.out_file, params.dist,
-                            params.threads_max, params.freqchunksize, params.workdir)
-    t_dist = time.perf_counter()
-    _timing("single process: distances%s %.3f s" % (" + container" if params.large in ("memmap", "h5py") else "", t_dist - t_dist0))
-    if params.out_freq_file:
-        print("Writing frequency matrix")
-        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
-    if not (params.mthdrun in ("joblib", "hip") and params.large != "None"):      # :1064
-        print("Writing distance matrix")
-        if res is not None:                  # None: unknown --method, nothing was computed (:552 only prints)
-            api.write_mat_text(params.out_file, res)
-    if params.json_stats and frequencies is not None:
-        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
-    return 0
-
-
-def _knn_single(params, frequencies, t_start, t_freq, t_dist0):
-    """--knn in one process: the graph from the integer profiles (po_knn, float64), written to -o"""
-    global LAST_STAGE2
-    if frequencies is None:
-        return 0
-    if params.dist not in METRICS:
-        print("Error, unknown metric methodfor joblib: {}".format(params.dist), file=sys.stderr)
-        sys.exit(1)
-    counts, totals = frequencies.counts, frequencies.totals
+def _tsne_mode(params, frequencies):
+    """--tsne: the graph as --knn int(3 p + 1) selects it (po_knn, float64), embedded by po_tsne, written to -o as text"""
     n = frequencies.shape[0]
-    idx, val, st = _context().knn(counts, totals, params.knn, params.dist, "float64", want_stats=True)
-    LAST_STAGE2 = dict(st, rows=[0, n])
-    t_dist = time.perf_counter()
-    _timing("single process: k-NN graph %.3f s" % (t_dist - t_dist0))
-    if params.out_freq_file:
-        print("Writing frequency matrix")
-        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
-    print("Writing distance matrix")
-    _write_knn(params, counts, idx, val)
-    if params.json_stats:
-        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
-    return 0
+    if n < 4:
+        refuse("Error, --tsne needs at least 4 contigs (got %d)" % n)
+    ctx = _context()
+    idx, val, st = ctx.knn(frequencies.counts, frequencies.totals, api.tsne_neighbours(n, params.tsne), params.dist, "float64", want_stats=True)
+    t0 = time.perf_counter()
+    try:
+        y, ts = ctx.tsne(idx, val, params.tsne, seed=params.tsne_seed, max_iter=params.tsne_iter, want_stats=True, metric=params.dist)
+    except api._lib.PhyloligoError as e:
+        refuse("Error, --tsne: %s" % e)
+    return ("k-NN graph + t-SNE", "Writing t-SNE embedding", lambda: np.savetxt(params.out_file, y), dict(st, rows=[0, n]),
+            {"tsne_ms": (time.perf_counter() - t0) * 1e3, "tsne_iterations": ts["iterations"], "tsne_kl": ts["kl"], "tsne_perplexity": params.tsne})
 
 
-LAST_CLIP = None         # the clip_* keys of the last --clip-percentile / --min-size run (what --json-stats reports)
-
-
-def _device_matrix(params, ctx, frequencies, f32, who):
+def _device_matrix(params, ctx, frequencies, f32, who, half):
     """the dense n x n matrix of the run's metric in device memory (po_pairwise_dev), rows on whole 128-byte lines: (buffer, ld,
-    stage-2 stats); exits with the sizes when it does not fit"""
+    stage-2 stats); exits with the sizes, and `half` as what would take half of them, when it does not fit"""
     import torch
     n = frequencies.shape[0]
     dev = torch.device("cuda", ctx.device)
@@ -845,10 +612,8 @@ def _device_matrix(params, ctx, frequencies, f32, who):
     try:
         buf = torch.empty((n, ld), dtype=torch.float32 if f32 else torch.float64, device=dev)
     except torch.cuda.OutOfMemoryError:
-        print("Error, %s: the %d x %d %s matrix (%.1f GB) does not fit the memory of the GPU%s"
-              % (who, n, n, name, n * ld * esz / 1e9, "" if f32 else "; a float32 matrix takes half (%.1f GB)" % (n * ld * 4 / 1e9)),
-              file=sys.stderr)
-        sys.exit(1)
+        refuse("Error, %s: the %d x %d %s matrix (%.1f GB) does not fit the memory of the GPU%s"
+               % (who, n, n, name, n * ld * esz / 1e9, "" if f32 else "; %s takes half (%.1f GB)" % (half, n * ld * 4 / 1e9)))
     d_counts = torch.from_numpy(np.ascontiguousarray(frequencies.counts).view(np.int32)).to(dev)
     d_totals = torch.from_numpy(np.ascontiguousarray(frequencies.totals).view(np.int64)).to(dev)
     _, st = ctx.pairwise(d_counts, d_totals, params.dist, dtype=name, out=buf, want_stats=True)
@@ -859,13 +624,8 @@ def _device_matrix(params, ctx, frequencies, f32, who):
 def _clip(params, frequencies):
     """--clip-percentile / --min-size (bin/phyloselect.R:339-357): the dense matrix computed into device memory, its row medians
     taken there (po_row_medians_dev), the two filters applied to those n doubles on the host; returns the profiles of the kept
-    records, in input order - everything after this runs as it would on an input that held only them."""
-    global LAST_CLIP
-    if frequencies is None:
-        return None
-    if params.dist not in METRICS:
-        print("Error, unknown metric methodfor joblib: {}".format(params.dist), file=sys.stderr)
-        sys.exit(1)
+    records, in input order - everything after this runs as it would on an input that held only them - and the clip_* keys of
+    --json-stats."""
     import torch
     print("Clipping outlier contigs")
     n = frequencies.shape[0]
@@ -875,7 +635,7 @@ def _clip(params, frequencies):
     medians = np.zeros(0)
     t1 = t2 = t0
     if n:
-        buf, _, _ = _device_matrix(params, ctx, frequencies, f32, "--clip-percentile")
+        buf, _, _ = _device_matrix(params, ctx, frequencies, f32, "--clip-percentile", "a float32 matrix")
         t1 = time.perf_counter()
         d_med = ctx.row_medians(buf[:, :n])
         torch.cuda.synchronize(d_med.device)
@@ -890,15 +650,13 @@ def _clip(params, frequencies):
         keep = api.clip_keep(medians, p, lengths, size)
         threshold = api.clip_threshold(medians, p) if p != 1 and n else None
     except api._lib.PhyloligoError as e:
-        print("Error, --clip-percentile: %s" % e, file=sys.stderr)
-        sys.exit(1)
-    LAST_CLIP = {"clip_percentile": p, "clip_min_size": size, "clip_threshold": threshold, "clip_kept": int(keep.size),
-                 "clip_dropped_by_median": int(n - by_median.size), "clip_dropped_by_size": int(by_median.size - keep.size),
-                 "clip_medians_ms": (t2 - t1) * 1e3, "clip_matrix_ms": (t1 - t0) * 1e3, "clip_dtype": "float32" if f32 else "float64",
-                 "clip_input_contigs": int(n)}
+        refuse("Error, --clip-percentile: %s" % e)
+    stats = {"clip_percentile": p, "clip_min_size": size, "clip_threshold": threshold, "clip_kept": int(keep.size),
+             "clip_dropped_by_median": int(n - by_median.size), "clip_dropped_by_size": int(by_median.size - keep.size),
+             "clip_medians_ms": (t2 - t1) * 1e3, "clip_matrix_ms": (t1 - t0) * 1e3, "clip_dtype": "float32" if f32 else "float64",
+             "clip_input_contigs": int(n)}
     if keep.size < 1:
-        print("Error, --clip-percentile %g --min-size %d keep none of the %d contigs" % (p, size, n), file=sys.stderr)
-        sys.exit(1)
+        refuse("Error, --clip-percentile %g --min-size %d keep none of the %d contigs" % (p, size, n))
     titles = frequencies.titles
     sweep = _sweep_range(params)
     downstream_runs = ((params.kmedoids is None or params.kmedoids <= keep.size) and (sweep is None or sweep[1] <= keep.size) and
@@ -909,45 +667,7 @@ def _clip(params, frequencies):
                 words = titles[int(i)].split()
                 fh.write("%d\t%s\t%d\t%.17g\n" % (i, words[0] if words else "", lengths[i], medians[i]))
     return ProfileMatrix(np.asarray(frequencies)[keep], frequencies.counts[keep], frequencies.totals[keep],
-                         [titles[int(i)] for i in keep], lengths[keep])
-
-
-LAST_TSNE = None         # tsne_ms / tsne_iterations / tsne_kl of the last --tsne run (what --json-stats reports)
-
-
-def _tsne_single(params, frequencies, t_start, t_freq, t_dist0):
-    """--tsne: the graph as --knn int(3 p + 1) selects it (po_knn, float64), embedded by po_tsne, written to -o as text"""
-    global LAST_STAGE2, LAST_TSNE
-    if frequencies is None:
-        return 0
-    counts, totals = frequencies.counts, frequencies.totals
-    n = frequencies.shape[0]
-    if n < 4:
-        print("Error, --tsne needs at least 4 contigs (got %d)" % n, file=sys.stderr)
-        sys.exit(1)
-    ctx = _context()
-    idx, val, st = ctx.knn(counts, totals, api.tsne_neighbours(n, params.tsne), params.dist, "float64", want_stats=True)
-    LAST_STAGE2 = dict(st, rows=[0, n])
-    t0 = time.perf_counter()
-    try:
-        y, ts = ctx.tsne(idx, val, params.tsne, seed=params.tsne_seed, max_iter=params.tsne_iter, want_stats=True, metric=params.dist)
-    except api._lib.PhyloligoError as e:
-        print("Error, --tsne: %s" % e, file=sys.stderr)
-        sys.exit(1)
-    t_dist = time.perf_counter()
-    LAST_TSNE = {"tsne_ms": (t_dist - t0) * 1e3, "tsne_iterations": ts["iterations"], "tsne_kl": ts["kl"]}
-    _timing("single process: k-NN graph + t-SNE %.3f s" % (t_dist - t_dist0))
-    if params.out_freq_file:
-        print("Writing frequency matrix")
-        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
-    print("Writing t-SNE embedding")
-    np.savetxt(params.out_file, y)
-    if params.json_stats:
-        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
-    return 0
-
-
-LAST_KMEDOIDS = None     # what --json-stats reports of the last --kmedoids run
+                         [titles[int(i)] for i in keep], lengths[keep]), stats
 
 
 def write_labels(path, labels):
@@ -991,44 +711,22 @@ def silhouette_cluster_means(values, labels, k):
     return [float(values[labels == c].mean()) if (labels == c).any() else None for c in range(k)]
 
 
-def _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0):
+def _kmedoids_mode(params, frequencies):
     """--kmedoids / --kmedoids-sweep: the dense matrix computed into device memory (po_pairwise_dev) once, clustered there
     (po_kmedoids_dev) for the one K or for every K of the range, each clustering scored there (po_silhouette_dev) when the run
     reports it; only labels, silhouette values and scalars come back"""
-    global LAST_STAGE2, LAST_KMEDOIDS
-    if frequencies is None:
-        return 0
-    import torch
     n = frequencies.shape[0]
     sweep = _sweep_range(params)
     if sweep is None:
         ks_wanted = [params.kmedoids]
         if not 1 <= params.kmedoids <= n:
-            print("Error, --kmedoids K needs 1 <= K <= number of contigs (got K = %d for %d contigs)" % (params.kmedoids, n), file=sys.stderr)
-            sys.exit(1)
+            refuse("Error, --kmedoids K needs 1 <= K <= number of contigs (got K = %d for %d contigs)" % (params.kmedoids, n))
     else:
         ks_wanted = list(range(sweep[0], sweep[1] + 1))
         if sweep[1] > n:
-            print("Error, --kmedoids-sweep LO:HI needs 2 <= LO <= HI <= number of contigs (got %d:%d for %d contigs)" % (sweep[0], sweep[1], n),
-                  file=sys.stderr)
-            sys.exit(1)
+            refuse("Error, --kmedoids-sweep LO:HI needs 2 <= LO <= HI <= number of contigs (got %d:%d for %d contigs)" % (sweep[0], sweep[1], n))
     ctx = _context()
-    dev = torch.device("cuda", ctx.device)
-    f32 = params.kmedoids_dtype == "float32"
-    esz = 4 if f32 else 8
-    ld = (n + 128 // esz - 1) // (128 // esz) * (128 // esz)            # rows on whole 128-byte lines
-    try:
-        buf = torch.empty((n, ld), dtype=torch.float32 if f32 else torch.float64, device=dev)
-    except torch.cuda.OutOfMemoryError:
-        print("Error, --kmedoids: the %d x %d %s matrix (%.1f GB) does not fit the memory of the GPU%s"
-              % (n, n, params.kmedoids_dtype, n * ld * esz / 1e9,
-                 "" if f32 else "; --kmedoids-dtype float32 takes half (%.1f GB)" % (n * ld * 4 / 1e9)), file=sys.stderr)
-        sys.exit(1)
-    d_counts = torch.from_numpy(np.ascontiguousarray(frequencies.counts).view(np.int32)).to(dev)
-    d_totals = torch.from_numpy(np.ascontiguousarray(frequencies.totals).view(np.int64)).to(dev)
-    _, st = ctx.pairwise(d_counts, d_totals, params.dist, dtype=params.kmedoids_dtype, out=buf, want_stats=True)
-    LAST_STAGE2 = dict(st, rows=[0, n])
-    torch.cuda.synchronize(dev)
+    buf, _, st = _device_matrix(params, ctx, frequencies, params.kmedoids_dtype == "float32", "--kmedoids", "--kmedoids-dtype float32")
     scored = sweep is not None or params.silhouette is not None or bool(params.json_stats)      # the mean costs one matrix read
     runs = []
     for k in ks_wanted:
@@ -1036,8 +734,7 @@ def _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0):
         try:
             d_labels, medoids, ks = ctx.kmedoids(buf[:, :n], k, max_iter=params.kmedoids_iter, want_stats=True)
         except api._lib.PhyloligoError as e:
-            print("Error, --kmedoids: %s" % e, file=sys.stderr)
-            sys.exit(1)
+            refuse("Error, --kmedoids: %s" % e)
         labels, medoids = d_labels.cpu().numpy(), medoids.cpu().numpy()
         t1 = time.perf_counter()
         run = {"labels": labels, "values": None,
@@ -1055,67 +752,93 @@ def _kmedoids_single(params, frequencies, t_start, t_freq, t_dist0):
                                     silhouette_ms=(time.perf_counter() - t1) * 1e3, silhouette_passes=ss["passes"])
             except api._lib.PhyloligoError as e:             # fewer than two clusters with a member: no silhouette
                 if sweep is None and params.silhouette is not None:
-                    print("Error, --silhouette: %s" % e, file=sys.stderr)
-                    sys.exit(1)
+                    refuse("Error, --silhouette: %s" % e)
                 run["stats"].update(silhouette_mean=None, silhouette_cluster_means=None, silhouette_ms=None, silhouette_passes=None)
         run["row"] = {"K": k, "iterations": ks["iterations"], "converged": ks["converged"], "empty_clusters": ks["empty_clusters"],
                       "inertia": ks["inertia"], "silhouette_mean": mean, "sizes": run["stats"]["kmedoids_sizes"]}
         runs.append(run)
+    rows = [r["row"] for r in runs]
     if sweep is None:
         best = runs[0]
-        LAST_KMEDOIDS = best["stats"]
+        stats = best["stats"]
     else:
-        rows = [r["row"] for r in runs]
         won = sweep_best(rows)
         if won is None:
-            print("Error, --kmedoids-sweep %s: the mean silhouette of every K is NaN (the matrix holds undefined distances)"
-                  % params.kmedoids_sweep, file=sys.stderr)
-            sys.exit(1)
+            refuse("Error, --kmedoids-sweep %s: the mean silhouette of every K is NaN (the matrix holds undefined distances)" % params.kmedoids_sweep)
         best = next(r for r in runs if r["row"] is won)
-        LAST_KMEDOIDS = dict(best["stats"], kmedoids_sweep=rows, kmedoids_sweep_best=won["K"])
+        stats = dict(best["stats"], kmedoids_sweep=rows, kmedoids_sweep_best=won["K"])
+
+    def write():
+        write_labels(params.out_file, best["labels"])
+        if params.silhouette is not None:
+            write_silhouette(params.silhouette, best["values"])
+        if sweep is not None and params.sweep_out is not None:
+            write_sweep_table(params.sweep_out, rows)
+
+    return "matrix + k-medoids", "Writing cluster labels", write, dict(st, rows=[0, n]), stats
+
+
+def main(argv=None, params=None):
+    """phyloligo.py:1036-1068 around whichever mode the options choose.  params: the command line as `python -m phyloligo_amd`
+    has parsed it already."""
+    global INGEST_PHASES
+    if params is None:
+        params = get_cmd(argv)
+    if type(params.pattern) == int:                      # :1040-1041
+        params.pattern = str("1") * params.pattern
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        from .cli_ranks import main_distributed
+        return main_distributed(params)
+    refuse(refusal(params))
+    t_start = time.perf_counter()
+    print("Using pattern {}".format(params.pattern))
+    if not os.path.isdir(params.workdir):
+        os.makedirs(params.workdir)
+    print("Computing frequencies")
+    INGEST_PHASES = bool(params.json_stats)              # the phase times of the ingest go into the JSON record
+    frequencies, freq_name = compute_frequencies(params.mthdrun, params.large, params.genome, params.pattern,
+                                                 params.strand, params.distchunksize, params.threads_max,
+                                                 params.workdir)
+    t_freq = time.perf_counter()
+    if frequencies is not None and params.dist not in METRICS:
+        refuse("Error, unknown metric methodfor joblib: {}".format(params.dist))
+    clipped = {}
+    if frequencies is not None and _clip_active(params):
+        frequencies, clipped = _clip(params, frequencies)
+    print("Computing Pairwise distances")
+    t_dist0 = time.perf_counter()
+    if frequencies is None:                              # an unknown --method: compute_frequencies has said so (:995 only prints)
+        return 0
+    mode = (_kmedoids_mode if params.kmedoids is not None or params.kmedoids_sweep is not None else
+            _tsne_mode if params.tsne is not None else _knn_mode if params.knn is not None else _matrix_mode)
+    label, announce, write, stage2, stats = mode(params, frequencies)
     t_dist = time.perf_counter()
-    _timing("single process: matrix + k-medoids %.3f s" % (t_dist - t_dist0))
-    if params.out_freq_file:
-        print("Writing frequency matrix")
-        api.write_mat_text(params.out_freq_file, np.asarray(frequencies))
-    print("Writing cluster labels")
-    write_labels(params.out_file, best["labels"])
-    if params.silhouette is not None:
-        write_silhouette(params.silhouette, best["values"])
-    if sweep is not None and params.sweep_out is not None:
-        write_sweep_table(params.sweep_out, [r["row"] for r in runs])
+    _timing("single process: %s %.3f s" % (label, t_dist - t_dist0))
+    _write_freq(params, lambda: np.asarray(frequencies))
+    if announce:
+        print(announce)
+        write()
     if params.json_stats:
-        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start)
+        _write_json_stats(params, frequencies, t_freq - t_start, t_dist - t_dist0, time.perf_counter() - t_dist, time.perf_counter() - t_start,
+                          stage2=stage2, stats=dict(stats, **clipped))
     return 0
 
 
-class _Shape:
-    """stands in for the frequency matrix where only its shape is wanted (--json-stats of a multi-rank run)"""
-
-    def __init__(self, n, dim):
-        self.shape = (n, dim)
-
-
-def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpus=1):
-    """--json-stats ("keep the same five lines for CLI fidelity; add --json-stats")"""
+def _write_json_stats(params, frequencies, freq_s, dist_s, write_s, total_s, gpus=1, stage2=None, stats={}):
+    """--json-stats ("keep the same five lines for CLI fidelity; add --json-stats"): the run's sizes and times, the
+    stats of its first stage-2 call, then the keys of its mode and of the clip.  frequencies: anything with the matrix's shape."""
     import json
     from . import _lib
     n, dim = (int(x) for x in frequencies.shape)
-    stats = {"library": _lib.load().po_version().decode(), "device": _context().device_name, "gpus": gpus,
-             "assembly": os.path.abspath(params.genome), "contigs": n, "words": dim, "pattern": str(params.pattern),
-             "strand": params.strand, "metric": params.dist, "large": params.large, "pairs": n * (n - 1) // 2,
-             "seconds": {"frequencies": freq_s, "distances" + ("_and_container" if params.large in ("memmap", "h5py") else ""): dist_s,
-                         "writing": write_s, "total": total_s},
-             "stage2_first_call": LAST_STAGE2,
-             **({} if getattr(params, "knn", None) is None else
-                {"knn": params.knn, "knn_select_ms": None if LAST_STAGE2 is None else LAST_STAGE2.get("select_ms")}),
-             **({} if getattr(params, "tsne", None) is None or LAST_TSNE is None else dict(LAST_TSNE, tsne_perplexity=params.tsne)),
-             **({} if (getattr(params, "kmedoids", None) is None and getattr(params, "kmedoids_sweep", None) is None) or LAST_KMEDOIDS is None
-                else LAST_KMEDOIDS),
-             **({} if not _clip_active(params) or LAST_CLIP is None else LAST_CLIP),
-             "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
+    record = {"library": _lib.load().po_version().decode(), "device": _context().device_name, "gpus": gpus,
+              "assembly": os.path.abspath(params.genome), "contigs": n, "words": dim, "pattern": str(params.pattern),
+              "strand": params.strand, "metric": params.dist, "large": params.large, "pairs": n * (n - 1) // 2,
+              "seconds": {"frequencies": freq_s, "distances" + ("_and_container" if params.large in ("memmap", "h5py") else ""): dist_s,
+                          "writing": write_s, "total": total_s},
+              "stage2_first_call": stage2, **stats,
+              "ingest_phases_ms": None if LAST_INGEST is None else {k: round(v, 3) for k, v in LAST_INGEST.items()}}
     with open(params.json_stats, "w") as fh:
-        json.dump(stats, fh, indent=1)
+        json.dump(record, fh, indent=1)
         fh.write("\n")
 
 

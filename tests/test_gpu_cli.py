@@ -333,6 +333,42 @@ def test_cli_process_runs_without_torch(fasta, tmp_path):
     assert open(raw_ref, "rb").read() == open(raw_got, "rb").read()
 
 
+def test_abbreviated_options_run_as_their_full_spelling(tmp_path):
+    """argparse accepts unambiguous prefixes of the options.  A sweep over a clipped matrix keeps it in a torch tensor, so torch has
+    to be in the process before the library is loaded, however the options are spelled: same labels from `--kmedoids-s --clip-p` as
+    from `--kmedoids-sweep --clip-percentile`, and torch is there at the moment the library is first loaded."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(12)
+    fa = tmp_path / "asm.fa"
+    with open(fa, "wb") as fh:
+        for i in range(12):
+            s = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=int(rng.integers(200, 601)))].tobytes()
+            fh.write(b">c%d\n" % i + s + b"\n")
+    code = ("import ctypes, sys, runpy\n"
+            "from phyloligo_amd import _lib\n"
+            "cdll = ctypes.CDLL\n"
+            "def loading(name, *a, **k):\n"
+            "    if name == _lib.LIB_PATH:\n        print('TORCH_AT_LOAD', 'torch' in sys.modules)\n"
+            "    return cdll(name, *a, **k)\n"
+            "ctypes.CDLL = loading\n"
+            "sys.argv = ['phyloligo_amd'] + sys.argv[1:]\n"
+            "try:\n    runpy.run_module('phyloligo_amd', run_name='__main__')\n"
+            "except SystemExit as e:\n    assert e.code in (0, None), e.code\n")
+    env = dict(os.environ, PYTHONPATH=root)
+    env.pop("WORLD_SIZE", None)
+    labels = {}
+    for name, sweep, clip in (("short", "--kmedoids-s", "--clip-p"), ("full", "--kmedoids-sweep", "--clip-percentile")):
+        out = tmp_path / (name + ".txt")
+        r = subprocess.run([sys.executable, "-c", code, "-i", str(fa), "--method", "joblib", sweep, "2:3", clip, "0.9", "-d", "Eucl",
+                            "-o", str(out)], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert r.stdout.count("TORCH_AT_LOAD") == 1 and "TORCH_AT_LOAD True" in r.stdout, r.stdout
+        labels[name] = out.read_bytes()
+    assert labels["short"] == labels["full"] and 10 <= labels["full"].count(b"\n") <= 12
+
+
 def test_json_stats(fasta, tmp_path, capsys):
     """--json-stats: sizes, phase times, library and device, the stage-2 kernel of the run - next to the
     five progress lines, which stay exactly the reference's."""
