@@ -22,7 +22,7 @@
 // conflict free.  The order of K inside the dot product is irrelevant as long as both operands agree.
 //
 // Eligibility is decided on the device from the largest |value| of the matrix: every candidate kernel is
-// launched and all but one exit at once (no host synchronisation); see po_api.hip.
+// launched and all but one exit at once (no host synchronisation); see prepare_eucl, po_pairwise.hip.
 #include "po_tiles.h"
 #include <type_traits>
 

@@ -38,6 +38,13 @@ void po_set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
         }                                                                                  \
     } while (0)
 
+// a call that returns a status: pass anything but PO_OK on to the caller
+#define PO_TRY(call)                                                                       \
+    do {                                                                                   \
+        int rc__ = (call);                                                                 \
+        if (rc__) return rc__;                                                             \
+    } while (0)
+
 // ---- context ---------------------------------------------------------------------------
 // A growable device buffer owned by the context: it only grows between po_ctx_trim / po_ctx_destroy (and the pair-dot operand
 // is released when a call for another metric follows), so the steady state of repeated calls does no hipMalloc.
@@ -50,10 +57,11 @@ struct po_ctx {
     int device = 0;
     hipStream_t stream = nullptr;      // caller's stream (not owned) or the default stream
     hipDeviceProp_t prop;
-    po_buf ws_freq;                    // Ft: float64 [dim][npad] transposed frequencies
+    // stage 2 (po_pairwise.hip): sized by reserve_pairwise, filled by prepare (step 2 of po_pairwise_run), read by launch_block (step 3)
+    po_buf ws_freq;                    // Ft: float64 [dim][npad] transposed frequencies (SC int8: doubled ranks; KT: pair-dot ranks / rank panels)
     po_buf ws_rowstat;                 // per-row terms (entropy, norm, ...), float64 [4][npad]
-    po_buf ws_aux;                     // metric specific (ranks, sign expansions, chunk tables)
-    po_buf ws_io;                      // staging of the host-pointer entry points
+    po_buf ws_aux;                     // metric specific (ranks, digit planes, chunk tables): what the metric's prepare_* function builds
+    po_buf ws_io;                      // staging of the host-pointer entry points, cut by po_stage (po_api.hip, po_pairwise.hip, po_knn.hip) or po_stage_host_matrix (po_rows.h)
     po_buf ws_logtab;                  // replicated log table of the JSD kernel
     bool logtab_ready = false;
     po_buf ws_fold;                    // reverse-complement folded counts / frequencies (po_fold.hip) + flag word
@@ -75,21 +83,22 @@ struct po_ctx {
     size_t h_blockmax_cap = 0;         // in words
     po_buf ws_tilelist;                // per-class tile lists of the int8 Gram path (po_gram_i8.hip)
     po_buf ws_fix;                     // po_fix_list of the JSD path (po_jsd_exact.hip)
-    po_buf ws_knn;                     // panel slab + mirror of the k-NN drivers (po_knn*): grown once per call shape
+    po_buf ws_knn;                     // panel slab + mirror of the k-NN drivers (knn_core, po_knn.hip): grown once per call shape
     po_buf ws_tsne_aff;                // t-SNE affinities: conditional probabilities and the temporary rows of the CSR (po_tsne.hip)
     po_buf ws_tsne;                    // t-SNE gradient / optimiser: partial sums, two embeddings, update, gains
-    po_buf ws_tsne_csr;                // po_tsne (host pointers): lists, CSR and embeddings on the device
+    po_buf ws_tsne_csr;                // po_tsne (host pointers, po_tsne.hip): lists, CSR and embeddings on the device
     double* h_tsne = nullptr;          // pinned: 8 doubles read back by the t-SNE entry points
     po_buf ws_kmed;                    // k-medoids: pair list (rows / medoids, labels / clusters), costs, per-cluster minima (po_kmedoids.hip)
     double* h_kmed = nullptr;          // pinned: 8 doubles read back by the k-medoids entry points
     po_buf ws_rowmed;                  // row medians: the counter of row reads of the last call (po_rowmedian.hip)
     po_buf ws_sil;                     // silhouettes: labels, cluster sizes, one pass's sums [n][PO_SILHOUETTE_CHUNK], two doubles per row (po_silhouette.hip)
     double* h_sil = nullptr;           // pinned: 8 doubles read back by the silhouette entry points
-    void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of the host-pointer entry points (device -> host rows)
+    void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of po_pairwise / po_pairwise_freq (copy_rows_to_host, po_pairwise.hip)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 int po_buf_reserve(po_ctx* ctx, po_buf* b, size_t bytes);
+void po_buf_free(po_buf* b);           // the caller has finished the work that uses it
 // hipFuncAttributeMaxDynamicSharedMemorySize for `func`, raised once per process and device (and again only if a
 // later launch asks for more; it never goes down): the attribute call is host work that does not belong in a launch path
 int po_func_shmem(po_ctx* ctx, const void* func, size_t bytes);
@@ -98,6 +107,74 @@ int po_func_shmem(po_ctx* ctx, const void* func, size_t bytes);
         int rc__ = po_func_shmem((ctx), reinterpret_cast<const void*>(kernel), (bytes));   \
         if (rc__) return rc__;                                                             \
     } while (0)
+
+static inline uint64_t po_round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
+
+// Cuts a workspace into arrays that start on 256-byte boundaries.  base NULL: only `off`, the bytes needed, is of use.
+struct po_carver {
+    uint8_t* base;
+    size_t off = 0;
+    uint8_t* take(size_t bytes) {
+        uint8_t* p = base ? base + off : nullptr;
+        off += po_round_up(bytes, 256);
+        return p;
+    }
+    template <typename T> T* array(size_t count) { return reinterpret_cast<T*>(take(count * sizeof(T))); }
+};
+
+// The device arrays of a host-pointer entry point: `layout(po_carver&)` names them.  It runs once on no memory for the size,
+// `buf` (ctx->ws_io) grows to that, and it runs again on the buffer.
+template <typename F>
+inline int po_stage(po_ctx* ctx, po_buf* buf, F&& layout) {
+    po_carver sizing{nullptr};
+    layout(sizing);
+    PO_TRY(po_buf_reserve(ctx, buf, sizing.off));
+    po_carver ws{static_cast<uint8_t*>(buf->p)};
+    layout(ws);
+    return PO_OK;
+}
+
+// the start of a host-pointer call on integer profiles: counts [n][dim] and totals [n] on their way to the device
+inline int po_upload_profiles(po_ctx* ctx, uint64_t n, uint32_t dim, const uint32_t* counts, const uint64_t* totals, uint32_t* d_cnt,
+                              uint64_t* d_tot) {
+    PO_HIP(hipMemcpyAsync(d_cnt, counts, n * (uint64_t)dim * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PO_HIP(hipMemcpyAsync(d_tot, totals, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    return PO_OK;
+}
+
+// ---- argument rules that several entry points state in the same words (who: the entry point named in the message) ----------
+#define PO_PAD_ROWS 128ull             // tile edge of the VALU / Gram kernels: rows of the working layout are padded to it
+inline int po_check_ctx(const char* who, const po_ctx* ctx) {
+    PO_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    return PO_OK;
+}
+inline int po_check_metric(int metric) {
+    // compute_distances_joblib prints "unknown metric" and exits(1) (phyloligo.py:383-385)
+    PO_REQUIRE(metric >= PO_EUCL && metric <= PO_SC, "unknown metric %d (Eucl=0, JSD=1, KT=2, BC=3, SC=4)", metric);
+    return PO_OK;
+}
+// what: the argument's name (out_dtype, val_dtype)
+inline int po_check_dtype(const char* who, const char* what, int dtype) {
+    PO_REQUIRE(dtype == PO_F64 || dtype == PO_F32, "%s: %s must be PO_F64 or PO_F32", who, what);
+    return PO_OK;
+}
+inline int po_check_dim(const char* who, uint32_t dim) {
+    PO_REQUIRE(dim >= 1, "%s: dim must be positive", who);
+    return PO_OK;
+}
+inline int po_check_knn_k(const char* who, uint32_t k) {
+    PO_REQUIRE(k >= 1 && k <= PO_KNN_MAX_K, "%s: k = %u outside 1..%u", who, k, PO_KNN_MAX_K);
+    return PO_OK;
+}
+// rows and columns of a block inside 0..n, in order (po_pairwise_blocks_dev and po_knn_blocks_dev word the refusal differently)
+inline bool po_block_inside(const po_block& b, uint64_t n) {
+    return b.row_begin <= b.row_end && b.row_end <= n && b.col_begin <= b.col_end && b.col_end <= n;
+}
+inline bool po_block_empty(const po_block& b) { return b.row_begin == b.row_end || b.col_begin == b.col_end; }
+inline int po_check_triangular_block(const char* who, uint32_t index, const po_block& b) {
+    PO_REQUIRE(b.row_begin == b.col_begin && b.row_end == b.col_end, "%s: block %u is triangular but rows != columns", who, index);
+    return PO_OK;
+}
 
 // ---- pattern ---------------------------------------------------------------------------
 #define PO_MAX_WINDOW 64
@@ -276,6 +353,14 @@ int po_launch_kt_panel_prep(po_ctx* ctx, const uint32_t* d_lessrank, uint64_t n,
                             po_kt_panel_plan* plan);
 int po_launch_kt_panel_tiles(po_ctx* ctx, const po_tile_args& a, const void* ws, const po_kt_panel_plan& plan, uint64_t* tiles);
 
+// The stage-2 driver (po_pairwise.hip): checks the call, prepares the working layout once, launches every block.  Exactly one of
+// (d_counts, d_totals) / d_freq is given.  after_block (may be NULL) is called behind the kernels of every non-empty block, on the
+// same stream: the k-NN drivers (po_knn.hip) consume a panel there before the next one overwrites it.
+typedef int (*po_after_block_fn)(void* user, uint32_t block);
+int po_pairwise_run(po_ctx* ctx, const char* who, const uint32_t* d_counts, const uint64_t* d_totals, const double* d_freq, uint64_t n,
+                    uint32_t dim, int metric, int out_dtype, const po_block* blocks, uint32_t n_blocks, uint32_t flags, po_stats* stats,
+                    po_after_block_fn after_block = nullptr, void* after_user = nullptr);
+
 // K nearest neighbours (po_knn.hip): one batch of candidate rows merged into the sorted lists idx int32 [n][k] / val [n][k]
 struct po_knn_batch {
     const void* src;          // candidate row t: src + t * ld (elements of the value type), len values
@@ -302,8 +387,6 @@ int po_launch_tsne_gradient(po_ctx* ctx, const int64_t* d_rowptr, const int32_t*
                             double exaggeration, void* ws, bool update, float* d_grad, float* d_y_out, float* d_upd, float* d_gains,
                             double momentum, double lr, double min_gain, bool want_kl, bool want_gn, double** d_scalars,
                             hipEvent_t* ev);   // ev (may be NULL): 4 events recorded before / after the repulsion, after Z, after the attraction
-
-static inline uint64_t po_round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 
 // Order-preserving unsigned keys of the selection kernels (po_knn.hip, po_rowmedian.hip): float32 / float64 bits with the sign
 // folded in (negative: all bits flipped; positive: sign bit set), -0 read as +0 so that the two zeros tie as numbers do, every

@@ -227,7 +227,7 @@ extern "C" int po_file_read(const char* path, uint8_t* buf, uint64_t len) {
     try { rcs.assign(nthr, PO_OK); } catch (const std::bad_alloc&) { po_set_error("po_file_read: out of host memory"); return PO_ENOMEM; }
     const int fd = open(path, O_RDONLY);
     if (fd < 0) { po_set_error("cannot open %s: %s", path, strerror(errno)); return PO_EIO; }
-    {   // a freshly allocated destination: ask for huge pages before the reader threads touch it (as in po_api.hip)
+    {   // a freshly allocated destination: ask for huge pages before the reader threads touch it (as in po_pairwise.hip)
         const uintptr_t lo = (reinterpret_cast<uintptr_t>(buf) + 4095u) & ~(uintptr_t)4095u;
         const uintptr_t hi = (reinterpret_cast<uintptr_t>(buf) + len) & ~(uintptr_t)4095u;
         if (hi > lo) (void)madvise(reinterpret_cast<void*>(lo), hi - lo, MADV_HUGEPAGE);

@@ -22,6 +22,8 @@
 // (float64), 32 KiB (float32) - four workgroups fit the 160 KiB of a CU.
 #include "po_rows.h"
 
+#include <vector>
+
 namespace {
 
 constexpr uint32_t kThreads = 256;
@@ -203,5 +205,265 @@ int po_launch_knn_select(po_ctx* ctx, int32_t* d_idx, void* d_val, uint32_t k, i
                            static_cast<const double*>(b.src), b.ld, b.cidx, b.ldc, b.row0, b.len, b.col0, b.diag, desc);
     }
     PO_CHECK_LAUNCH("knn_select_kernel");
+    return PO_OK;
+}
+
+// ---- the entry points ----------------------------------------------------------------------------------------------------
+// The lists are selected from panels of the matrix that po_pairwise_run computes into the context's workspace (ws_knn): a
+// triangular block [a,b) becomes row panels [lo,hi) = one triangular block plus the rectangle [lo,hi) x [hi,b) with its
+// mirror, a rectangular block becomes row strips with their mirrors.  Behind the kernels of the last block of a panel, the
+// panel's rows (slab) and the rows of its columns (mirror) are merged into the lists; the next panel reuses the
+// workspace.  Every ordered pair is fed exactly once, with the value the dense matrix holds.
+static const uint64_t kKnnPanelBytes = 256ull << 20;    // slab + mirror of one panel: about the Infinity Cache
+
+struct knn_feed {
+    po_knn_batch rows, cols;   // the panel's rows from the slab, the rows of its columns from the mirror (rows == 0: none)
+};
+
+struct knn_run {
+    po_ctx* ctx;
+    int32_t* idx;
+    void* val;
+    uint32_t k;
+    int f32, desc;
+    std::vector<po_block> panels;             // the blocks po_pairwise_run computes
+    std::vector<knn_feed> feeds;              // one per panel
+    std::vector<hipEvent_t> ev;               // selection start / end per panel when timed
+    std::vector<uint8_t> fed;
+    ~knn_run() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+static int knn_after_block(void* user, uint32_t b) {
+    knn_run* r = static_cast<knn_run*>(user);
+    const knn_feed& f = r->feeds[b];
+    if (f.rows.rows == 0 && f.cols.rows == 0) return PO_OK;
+    if (!r->ev.empty()) PO_HIP(hipEventRecord(r->ev[2 * b], r->ctx->stream));
+    PO_TRY(po_launch_knn_select(r->ctx, r->idx, r->val, r->k, r->f32, r->desc, f.rows));
+    PO_TRY(po_launch_knn_select(r->ctx, r->idx, r->val, r->k, r->f32, r->desc, f.cols));
+    if (!r->ev.empty()) {
+        PO_HIP(hipEventRecord(r->ev[2 * b + 1], r->ctx->stream));
+        r->fed[b] = 1;
+    }
+    return PO_OK;
+}
+
+// the blocks of a work list: inside 0..n, beginning on tile edges, triangular or off the diagonal; the tallest and the widest
+static int knn_check_blocks(const char* who, const po_block* blocks, uint32_t n_blocks, uint64_t n, uint64_t* max_rows, uint64_t* max_cols) {
+    *max_rows = *max_cols = 0;
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        const po_block& q = blocks[b];
+        PO_REQUIRE(po_block_inside(q, n), "%s: block %u outside 0..%llu", who, b, (unsigned long long)n);
+        PO_REQUIRE(q.row_begin % PO_PAD_ROWS == 0 && q.col_begin % PO_PAD_ROWS == 0,
+                   "%s: block %u does not begin on a multiple of %llu", who, b, (unsigned long long)PO_PAD_ROWS);
+        if (q.triangular)
+            PO_TRY(po_check_triangular_block(who, b, q));
+        else
+            PO_REQUIRE(q.row_end <= q.col_begin || q.col_end <= q.row_begin,
+                       "%s: rectangular block %u overlaps the diagonal (rows and columns must be disjoint)", who, b);
+        if (q.row_end - q.row_begin > *max_rows) *max_rows = q.row_end - q.row_begin;
+        if (q.col_end - q.col_begin > *max_cols) *max_cols = q.col_end - q.col_begin;
+    }
+    return PO_OK;
+}
+
+// cuts the work list into panels of h rows over the slab (row stride ld_s) and the mirror (ld_m), with what each feeds
+static void knn_plan_panels(knn_run& run, const po_block* blocks, uint32_t n_blocks, uint64_t h, uint8_t* slab, uint64_t ld_s,
+                            uint8_t* mirror, uint64_t ld_m, size_t esz) {
+    auto batch = [&](const uint8_t* src, uint64_t ld, uint64_t row0, uint64_t rows, uint64_t col0, uint64_t len, int diag) {
+        po_knn_batch q;
+        memset(&q, 0, sizeof(q));
+        q.src = src; q.ld = ld; q.row0 = row0; q.rows = rows;
+        q.col0 = (uint32_t)col0; q.len = (uint32_t)len; q.diag = diag;
+        return q;
+    };
+    auto add = [&](uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1, uint64_t out_col, bool tri, bool with_mirror, const knn_feed& f) {
+        po_block q;
+        memset(&q, 0, sizeof(q));
+        q.row_begin = r0; q.row_end = r1; q.col_begin = c0; q.col_end = c1;
+        q.out = slab + out_col * esz;
+        q.ld_out = ld_s;
+        q.mirror = with_mirror ? mirror : nullptr;
+        q.ld_mirror = ld_m;
+        q.triangular = tri ? 1u : 0u;
+        run.panels.push_back(q);
+        run.feeds.push_back(f);
+    };
+    const knn_feed none = {};
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        const po_block& q = blocks[b];
+        if (po_block_empty(q)) continue;
+        if (q.triangular) {
+            const uint64_t a = q.row_begin, e = q.row_end;
+            for (uint64_t lo = a; lo < e; lo += h) {
+                const uint64_t hi = lo + h < e ? lo + h : e;
+                knn_feed f;
+                f.rows = batch(slab, ld_s, lo, hi - lo, lo, e - lo, 1);
+                f.cols = batch(mirror, ld_m, hi, e - hi, lo, hi - lo, 0);
+                if (hi == e) {
+                    add(lo, hi, lo, hi, 0, true, false, f);
+                } else {
+                    add(lo, hi, lo, hi, 0, true, false, none);
+                    add(lo, hi, hi, e, hi - lo, false, true, f);
+                }
+            }
+        } else {
+            for (uint64_t s = q.row_begin; s < q.row_end; s += h) {
+                const uint64_t t = s + h < q.row_end ? s + h : q.row_end;
+                knn_feed f;
+                f.rows = batch(slab, ld_s, s, t - s, q.col_begin, q.col_end - q.col_begin, 0);
+                f.cols = batch(mirror, ld_m, q.col_begin, q.col_end - q.col_begin, s, t - s, 0);
+                add(s, t, q.col_begin, q.col_end, 0, false, true, f);
+            }
+        }
+    }
+}
+
+// k_eff of the ABI: min(k, n - 1), 0 for n <= 1 (an empty result)
+static uint32_t knn_k_eff(uint64_t n, uint32_t k) { return n > 1 ? (uint32_t)(k < n - 1 ? k : n - 1) : 0; }
+
+// knn over a list of blocks (pair ranges, out / mirror ignored); the lists [n][k_eff] are emptied first
+static int knn_core(po_ctx* ctx, const char* who, const uint32_t* d_counts, const uint64_t* d_totals, uint64_t n, uint32_t dim,
+                    int metric, uint32_t k, int val_dtype, uint64_t panel_rows, const po_block* blocks, uint32_t n_blocks,
+                    int32_t* d_idx, void* d_val, uint32_t flags, po_stats* stats) {
+    PO_TRY(po_check_ctx(who, ctx));
+    if (stats) memset(stats, 0, sizeof(*stats));
+    PO_TRY(po_check_metric(metric));
+    PO_TRY(po_check_knn_k(who, k));
+    PO_TRY(po_check_dtype(who, "val_dtype", val_dtype));
+    PO_REQUIRE(panel_rows % PO_PAD_ROWS == 0, "%s: panel_rows (%llu) is not a multiple of %llu", who,
+               (unsigned long long)panel_rows, (unsigned long long)PO_PAD_ROWS);
+    PO_REQUIRE(blocks != nullptr || n_blocks == 0, "%s: NULL block list", who);
+    PO_REQUIRE(n < (1ull << 31), "%s: n (%llu) does not fit the int32 neighbour indices", who, (unsigned long long)n);
+    const uint32_t k_eff = knn_k_eff(n, k);
+    if (k_eff == 0) return PO_OK;
+    PO_REQUIRE(d_counts != nullptr && d_totals != nullptr && d_idx != nullptr && d_val != nullptr, "%s: NULL buffer", who);
+    PO_TRY(po_check_dim(who, dim));
+    uint64_t max_rows = 0, max_cols = 0;
+    PO_TRY(knn_check_blocks(who, blocks, n_blocks, n, &max_rows, &max_cols));
+    PO_HIP(hipSetDevice(ctx->device));
+    const size_t esz = val_dtype == PO_F32 ? 4 : 8;
+    PO_HIP(hipMemsetAsync(d_idx, 0xFF, n * (uint64_t)k_eff * sizeof(int32_t), ctx->stream));      // every entry unused
+    PO_HIP(hipMemsetAsync(d_val, 0, n * (uint64_t)k_eff * esz, ctx->stream));
+    if (max_rows == 0 || max_cols == 0) return PO_OK;
+
+    // panel height: given, or the slab + mirror near kKnnPanelBytes (a multiple of the tile edge, so that the tiles are those of
+    // the dense matrix), never more than the tallest block
+    const uint64_t ld_s = po_round_up(max_cols, 32);
+    uint64_t h = panel_rows;
+    if (h == 0) {
+        h = kKnnPanelBytes / (esz * (ld_s + max_cols)) / PO_PAD_ROWS * PO_PAD_ROWS;
+        if (h < PO_PAD_ROWS) h = PO_PAD_ROWS;
+    }
+    if (h > po_round_up(max_rows, PO_PAD_ROWS)) h = po_round_up(max_rows, PO_PAD_ROWS);
+    const uint64_t ld_m = po_round_up(h, 32);
+    const size_t slab_bytes = po_round_up(h * ld_s * esz, 256);
+    PO_TRY(po_buf_reserve(ctx, &ctx->ws_knn, slab_bytes + max_cols * ld_m * esz));
+    uint8_t* slab = static_cast<uint8_t*>(ctx->ws_knn.p);
+
+    knn_run run;
+    run.ctx = ctx; run.idx = d_idx; run.val = d_val; run.k = k_eff;
+    run.f32 = val_dtype == PO_F32; run.desc = metric == PO_KT;
+    knn_plan_panels(run, blocks, n_blocks, h, slab, ld_s, slab + slab_bytes, ld_m, esz);
+    if (stats) {
+        run.ev.resize(2 * run.panels.size(), nullptr);
+        run.fed.assign(run.panels.size(), 0);
+        for (hipEvent_t& e : run.ev)
+            if (hipEventCreate(&e) != hipSuccess) {
+                po_set_error("%s: hipEventCreate failed", who);
+                return PO_EHIP;
+            }
+    }
+    // the dense symmetric path's convention: pairs are evaluated once; PO_FLAG_NO_SYMMETRY does not apply to a list
+    const int rc = po_pairwise_run(ctx, who, d_counts, d_totals, nullptr, n, dim, metric, val_dtype, run.panels.data(),
+                                   (uint32_t)run.panels.size(), flags & ~PO_FLAG_NO_SYMMETRY, stats, knn_after_block, &run);
+    if (stats && rc == PO_OK) {       // kernel_ms is the tile kernels alone: take the selections out
+        double sel = 0.0;
+        for (size_t b = 0; b < run.fed.size(); ++b) {
+            if (!run.fed[b]) continue;
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, run.ev[2 * b], run.ev[2 * b + 1]) == hipSuccess) sel += ms;
+        }
+        stats->kernel_ms = stats->kernel_ms > sel ? stats->kernel_ms - sel : 0.0;
+    }
+    return rc;
+}
+
+extern "C" int po_knn_dev(po_ctx* ctx, const uint32_t* d_counts, const uint64_t* d_totals, uint64_t n, uint32_t dim, int metric,
+                          uint32_t k, int val_dtype, uint64_t panel_rows, int32_t* d_idx, void* d_val, uint32_t flags,
+                          po_stats* stats) {
+    po_block whole;
+    memset(&whole, 0, sizeof(whole));
+    whole.row_end = whole.col_end = n;
+    whole.triangular = 1;
+    return knn_core(ctx, "po_knn_dev", d_counts, d_totals, n, dim, metric, k, val_dtype, panel_rows, &whole, 1, d_idx, d_val,
+                    flags, stats);
+}
+
+extern "C" int po_knn_blocks_dev(po_ctx* ctx, const uint32_t* d_counts, const uint64_t* d_totals, uint64_t n, uint32_t dim,
+                                 int metric, uint32_t k, int val_dtype, uint64_t panel_rows, const po_block* blocks,
+                                 uint32_t n_blocks, int32_t* d_idx, void* d_val, uint32_t flags, po_stats* stats) {
+    return knn_core(ctx, "po_knn_blocks_dev", d_counts, d_totals, n, dim, metric, k, val_dtype, panel_rows, blocks, n_blocks,
+                    d_idx, d_val, flags, stats);
+}
+
+extern "C" int po_knn_merge_dev(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* d_idx_in,
+                                const void* d_val_in, uint32_t m, int32_t* d_idx, void* d_val) {
+    PO_TRY(po_check_ctx("po_knn_merge_dev", ctx));
+    PO_TRY(po_check_metric(metric));
+    PO_TRY(po_check_knn_k("po_knn_merge_dev", k));
+    PO_TRY(po_check_dtype("po_knn_merge_dev", "val_dtype", val_dtype));
+    if (n == 0) return PO_OK;
+    PO_REQUIRE(d_idx != nullptr && d_val != nullptr && (m == 0 || (d_idx_in != nullptr && d_val_in != nullptr)),
+               "po_knn_merge_dev: NULL buffer");
+    PO_HIP(hipSetDevice(ctx->device));
+    const size_t esz = val_dtype == PO_F32 ? 4 : 8;
+    PO_HIP(hipMemsetAsync(d_idx, 0xFF, n * (uint64_t)k * sizeof(int32_t), ctx->stream));
+    PO_HIP(hipMemsetAsync(d_val, 0, n * (uint64_t)k * esz, ctx->stream));
+    for (uint32_t i = 0; i < m; ++i) {
+        po_knn_batch q;
+        memset(&q, 0, sizeof(q));
+        q.src = static_cast<const uint8_t*>(d_val_in) + (uint64_t)i * n * k * esz;
+        q.ld = k;
+        q.cidx = d_idx_in + (uint64_t)i * n * k;
+        q.ldc = k;
+        q.row0 = 0;
+        q.rows = n;
+        q.len = k;
+        PO_TRY(po_launch_knn_select(ctx, d_idx, d_val, k, val_dtype == PO_F32, metric == PO_KT, q));
+    }
+    return PO_OK;
+}
+
+// The host-pointer form stages and calls po_knn_dev.  The checks that come before the staging (it needs k_eff and the buffers)
+// name this entry point; everything after them is po_knn_dev's to refuse.
+extern "C" int po_knn(po_ctx* ctx, const uint32_t* counts, const uint64_t* totals, uint64_t n, uint32_t dim, int metric, uint32_t k,
+                      int val_dtype, uint64_t panel_rows, int32_t* idx, void* val, uint32_t flags, po_stats* stats) {
+    PO_TRY(po_check_ctx("po_knn", ctx));
+    if (stats) memset(stats, 0, sizeof(*stats));
+    PO_TRY(po_check_metric(metric));
+    PO_TRY(po_check_knn_k("po_knn", k));
+    PO_TRY(po_check_dtype("po_knn", "val_dtype", val_dtype));
+    const uint32_t k_eff = knn_k_eff(n, k);
+    if (k_eff == 0) return PO_OK;
+    PO_REQUIRE(counts != nullptr && totals != nullptr && idx != nullptr && val != nullptr, "po_knn: NULL buffer");
+    PO_TRY(po_check_dim("po_knn", dim));
+    PO_HIP(hipSetDevice(ctx->device));
+    const size_t esz = val_dtype == PO_F32 ? 4 : 8;
+    const uint64_t entries = n * (uint64_t)k_eff;
+    uint32_t* d_in = nullptr;
+    uint64_t* d_tot = nullptr;
+    int32_t* d_idx = nullptr;
+    uint8_t* d_val = nullptr;
+    PO_TRY(po_stage(ctx, &ctx->ws_io, [&](po_carver& ws) {
+        d_in = ws.array<uint32_t>(n * (uint64_t)dim);
+        d_tot = ws.array<uint64_t>(n);
+        d_idx = ws.array<int32_t>(entries);
+        d_val = ws.take(entries * esz);
+    }));
+    PO_TRY(po_upload_profiles(ctx, n, dim, counts, totals, d_in, d_tot));
+    PO_TRY(po_knn_dev(ctx, d_in, d_tot, n, dim, metric, k, val_dtype, panel_rows, d_idx, d_val, flags, stats));
+    PO_HIP(hipMemcpyAsync(idx, d_idx, entries * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PO_HIP(hipMemcpyAsync(val, d_val, entries * esz, hipMemcpyDeviceToHost, ctx->stream));
+    PO_HIP(hipStreamSynchronize(ctx->stream));
     return PO_OK;
 }

@@ -97,17 +97,6 @@ inline int po_check_matrix_args(const char* who, po_ctx* ctx, const void* m, int
     return PO_OK;
 }
 
-// Cuts a workspace into arrays that start on 256-byte boundaries.  base NULL: only `off`, the bytes needed, is of use.
-struct po_carver {
-    uint8_t* base;
-    size_t off = 0;
-    uint8_t* take(size_t bytes) {
-        uint8_t* p = base ? base + off : nullptr;
-        off += po_round_up(bytes, 256);
-        return p;
-    }
-};
-
 // device values v[count] all inside [0, limit)?  d_flag_word: a device word of the caller's workspace, h_word: a pinned host
 // word.  One synchronisation.  *bad: the first offending position or 0xFFFFFFFF.  (po_kmedoids.hip)
 int po_check_index_range(po_ctx* ctx, uint32_t* d_flag_word, uint32_t* h_word, const int32_t* v, uint32_t count, uint32_t limit, uint32_t* bad);

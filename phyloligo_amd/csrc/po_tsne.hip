@@ -25,6 +25,9 @@
 #include <float.h>
 #include <math.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "po_internal.h"
 
 namespace {
@@ -548,5 +551,290 @@ int po_launch_tsne_joint(po_ctx* ctx, uint64_t n, uint32_t k, const int32_t* d_i
     }
     hipLaunchKernelGGL(tsne_place_kernel, dim3((uint32_t)n), dim3(256), 0, ctx->stream, tptr, tcol, tval, total, d_rowptr, d_col, d_p);
     PO_CHECK_LAUNCH("tsne_place_kernel");
+    return PO_OK;
+}
+
+// ---- the entry points ----------------------------------------------------------------------------------------------------
+static int tsne_pinned(po_ctx* ctx) {
+    if (!ctx->h_tsne) PO_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_tsne), 8 * sizeof(double), hipHostMallocDefault));
+    return PO_OK;
+}
+
+static int check_tsne_lists(const char* who, uint64_t n, uint32_t k, int metric, int val_dtype, double perplexity) {
+    PO_TRY(po_check_metric(metric));
+    PO_REQUIRE(metric != PO_KT, "%s: metric KT is a correlation (lists ordered descending), not a distance: t-SNE cannot take it", who);
+    PO_TRY(po_check_dtype(who, "val_dtype", val_dtype));
+    PO_REQUIRE(perplexity >= 1.0, "%s: perplexity %g is below 1", who, perplexity);      // NaN fails this too
+    PO_REQUIRE(3.0 * perplexity + 1.0 < (double)PO_KNN_MAX_K + 1.0,
+               "%s: perplexity %g needs int(3 * perplexity + 1) = %.0f neighbours, more than PO_KNN_MAX_K = %u (perplexity <= %u)", who,
+               perplexity, floor(3.0 * perplexity + 1.0), PO_KNN_MAX_K, (PO_KNN_MAX_K - 1) / 3);
+    PO_REQUIRE(n >= 4, "%s: n = %llu, t-SNE needs at least 4 points", who, (unsigned long long)n);
+    PO_REQUIRE(n < (1ull << 31), "%s: n = %llu does not fit int32 indices", who, (unsigned long long)n);
+    const uint64_t want = (uint64_t)(3.0 * perplexity + 1.0);
+    const uint64_t k_want = want < n - 1 ? want : n - 1;
+    PO_REQUIRE(k == k_want, "%s: k = %u, but perplexity %g on %llu points takes min(n - 1, int(3 * perplexity + 1)) = %llu neighbours", who,
+               k, perplexity, (unsigned long long)n, (unsigned long long)k_want);
+    return PO_OK;
+}
+
+extern "C" int po_tsne_affinities_dev(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* d_idx,
+                                      const void* d_val, double perplexity, double* d_beta, double* d_cond, int64_t* d_rowptr,
+                                      int32_t* d_col, float* d_p, uint64_t cap, uint64_t* nnz) {
+    const char* who = "po_tsne_affinities_dev";
+    PO_TRY(po_check_ctx(who, ctx));
+    if (nnz) *nnz = 0;
+    PO_TRY(check_tsne_lists(who, n, k, metric, val_dtype, perplexity));
+    PO_REQUIRE(d_idx != nullptr && d_val != nullptr && d_rowptr != nullptr && d_col != nullptr && d_p != nullptr && nnz != nullptr,
+               "%s: NULL buffer", who);
+    PO_HIP(hipSetDevice(ctx->device));
+    PO_TRY(tsne_pinned(ctx));
+    PO_TRY(po_buf_reserve(ctx, &ctx->ws_tsne_aff, po_tsne_affinity_workspace(n, k)));
+    uint32_t* h_err = reinterpret_cast<uint32_t*>(ctx->h_tsne);
+    PO_TRY(po_launch_tsne_affinities(ctx, n, k, val_dtype == PO_F32, d_idx, d_val, perplexity, d_beta, d_cond, ctx->ws_tsne_aff.p, h_err));
+    PO_REQUIRE(h_err[2] == 0xFFFFFFFFu, "%s: row %u lists a neighbour index outside 0..n-1 or itself (an unfilled list?)", who, h_err[2]);
+    PO_REQUIRE(h_err[0] == 0xFFFFFFFFu, "%s: row %u has a NaN neighbour value (an empty record under BC / SC?)", who, h_err[0]);
+    PO_REQUIRE(h_err[1] == 0xFFFFFFFFu, "%s: row %u has a negative neighbour value: t-SNE needs distances", who, h_err[1]);
+    int64_t* h_nnz = reinterpret_cast<int64_t*>(ctx->h_tsne + 2);
+    uint32_t* h_dup = reinterpret_cast<uint32_t*>(ctx->h_tsne + 3);
+    PO_TRY(po_launch_tsne_joint(ctx, n, k, d_idx, ctx->ws_tsne_aff.p, d_rowptr, d_col, d_p, 0, h_nnz, h_dup));
+    PO_REQUIRE(*h_dup == 0xFFFFFFFFu, "%s: row %u lists a neighbour twice", who, *h_dup);
+    *nnz = (uint64_t)*h_nnz;
+    PO_REQUIRE(*nnz <= cap, "%s: the CSR has %llu entries, col / p hold %llu", who, (unsigned long long)*nnz, (unsigned long long)cap);
+    return po_launch_tsne_joint(ctx, n, k, d_idx, ctx->ws_tsne_aff.p, d_rowptr, d_col, d_p, 1, h_nnz, h_dup);
+}
+
+// the caller's CSR indexes y: its extents and columns are checked on the device before a kernel follows them
+static int tsne_check_csr(po_ctx* ctx, const char* who, uint64_t n, const int64_t* d_rowptr, const int32_t* d_col, uint64_t nnz, void* ws) {
+    uint32_t* d_err = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws) + po_tsne_grad_workspace(n));
+    uint32_t* h_err = reinterpret_cast<uint32_t*>(ctx->h_tsne);
+    PO_HIP(hipMemsetAsync(d_err, 0xFF, 4, ctx->stream));
+    PO_TRY(po_launch_tsne_check_csr(ctx, d_rowptr, d_col, n, nnz, d_err));
+    PO_HIP(hipMemcpyAsync(h_err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PO_HIP(hipStreamSynchronize(ctx->stream));
+    PO_REQUIRE(h_err[0] == 0xFFFFFFFFu, "%s: row %u of the CSR has row pointers outside 0..nnz or a column outside 0..n-1", who, h_err[0]);
+    return PO_OK;
+}
+
+extern "C" int po_tsne_gradient_dev(po_ctx* ctx, uint64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_p, uint64_t nnz,
+                                    const float* d_y, double exaggeration, float* d_grad, double* z, double* kl) {
+    const char* who = "po_tsne_gradient_dev";
+    PO_TRY(po_check_ctx(who, ctx));
+    PO_REQUIRE(n >= 1 && n < (1ull << 31), "%s: n = %llu out of range", who, (unsigned long long)n);
+    PO_REQUIRE(d_rowptr != nullptr && d_y != nullptr && d_grad != nullptr && (nnz == 0 || (d_col != nullptr && d_p != nullptr)),
+               "%s: NULL buffer", who);
+    PO_REQUIRE(exaggeration > 0.0, "%s: exaggeration must be positive", who);
+    PO_HIP(hipSetDevice(ctx->device));
+    PO_TRY(tsne_pinned(ctx));
+    PO_TRY(po_buf_reserve(ctx, &ctx->ws_tsne, po_tsne_grad_workspace(n) + 256));
+    PO_TRY(tsne_check_csr(ctx, who, n, d_rowptr, d_col, nnz, ctx->ws_tsne.p));
+    double* scal = nullptr;
+    PO_TRY(po_launch_tsne_gradient(ctx, d_rowptr, d_col, d_p, d_y, n, exaggeration, ctx->ws_tsne.p, false, d_grad, nullptr, nullptr, nullptr,
+                                   0.0, 0.0, 0.0, kl != nullptr, false, &scal, nullptr));
+    if (z || kl) {
+        PO_HIP(hipMemcpyAsync(ctx->h_tsne, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PO_HIP(hipStreamSynchronize(ctx->stream));
+        if (z) *z = ctx->h_tsne[0];
+        if (kl) *kl = ctx->h_tsne[1];
+    }
+    return PO_OK;
+}
+
+// a zero in po_tsne_params selects scikit-learn's value
+static int tsne_params(const char* who, uint64_t n, const po_tsne_params* params, po_tsne_params* out) {
+    po_tsne_params p;
+    memset(&p, 0, sizeof(p));
+    if (params) p = *params;
+    if (p.max_iter == 0) p.max_iter = 1000;
+    if (p.exploration_iter == 0) p.exploration_iter = 250;
+    if (p.n_iter_check == 0) p.n_iter_check = 50;
+    if (p.n_iter_without_progress == 0) p.n_iter_without_progress = 300;
+    if (p.early_exaggeration == 0.0) p.early_exaggeration = 12.0;
+    if (p.min_grad_norm == 0.0) p.min_grad_norm = 1e-7;
+    PO_REQUIRE(p.early_exaggeration >= 1.0, "%s: early_exaggeration %g is below 1", who, p.early_exaggeration);
+    if (p.learning_rate == 0.0) {
+        p.learning_rate = (double)n / p.early_exaggeration / 4.0;
+        if (p.learning_rate < 50.0) p.learning_rate = 50.0;
+    }
+    PO_REQUIRE(p.learning_rate > 0.0 && p.min_grad_norm > 0.0, "%s: learning_rate and min_grad_norm must be positive", who);
+    *out = p;
+    return PO_OK;
+}
+
+// time_kernels: four events per iteration, read after the loop (no extra synchronisation inside it)
+struct tsne_events {
+    std::vector<hipEvent_t> ev;
+    ~tsne_events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    int add4() {
+        for (int q = 0; q < 4; ++q) {
+            hipEvent_t e;
+            PO_HIP(hipEventCreate(&e));
+            ev.push_back(e);
+        }
+        return PO_OK;
+    }
+    // medians over the iterations; the rest of an iteration: start to the next start, less the two kernels
+    int medians(uint32_t steps, po_tsne_result* result) const {
+        std::vector<float> rep, att, rest;
+        for (uint32_t i = 0; i + 1 < steps; ++i) {
+            float a = 0.0f, b = 0.0f, c = 0.0f;
+            PO_HIP(hipEventElapsedTime(&a, ev[4 * i], ev[4 * i + 1]));
+            PO_HIP(hipEventElapsedTime(&b, ev[4 * i + 2], ev[4 * i + 3]));
+            PO_HIP(hipEventElapsedTime(&c, ev[4 * i], ev[4 * i + 4]));
+            rep.push_back(a);
+            att.push_back(b);
+            rest.push_back(c - a - b);
+        }
+        auto median = [](std::vector<float>& v) { std::sort(v.begin(), v.end()); return (double)v[v.size() / 2]; };
+        result->repulsion_ms = median(rep);
+        result->attraction_ms = median(att);
+        result->rest_ms = median(rest);
+        return PO_OK;
+    }
+};
+
+// csr_checked: the CSR was built by po_tsne_affinities_dev in this call (po_tsne), so it is not validated again
+static int tsne_run(po_ctx* ctx, const char* who, uint64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_p, uint64_t nnz,
+                    const float* d_y0, const po_tsne_params* params, float* d_y, po_tsne_result* result, bool csr_checked) {
+    PO_TRY(po_check_ctx(who, ctx));
+    if (result) memset(result, 0, sizeof(*result));
+    PO_REQUIRE(n >= 4 && n < (1ull << 31), "%s: n = %llu, t-SNE needs at least 4 points (and int32 indices)", who, (unsigned long long)n);
+    PO_REQUIRE(d_rowptr != nullptr && d_y0 != nullptr && d_y != nullptr && (nnz == 0 || (d_col != nullptr && d_p != nullptr)),
+               "%s: NULL buffer", who);
+    po_tsne_params p;
+    PO_TRY(tsne_params(who, n, params, &p));
+    PO_HIP(hipSetDevice(ctx->device));
+    PO_TRY(tsne_pinned(ctx));
+    uint8_t* base = nullptr;                   // the gradient's workspace, then two embeddings, the update and the gains
+    float *ybuf[2] = {nullptr, nullptr}, *upd = nullptr, *gains = nullptr;
+    PO_TRY(po_stage(ctx, &ctx->ws_tsne, [&](po_carver& ws) {
+        base = ws.take(po_tsne_grad_workspace(n) + 256);
+        ybuf[0] = ws.array<float>(n * 2);
+        ybuf[1] = ws.array<float>(n * 2);
+        upd = ws.array<float>(n * 2);
+        gains = ws.array<float>(n * 2);
+    }));
+    if (!csr_checked) PO_TRY(tsne_check_csr(ctx, who, n, d_rowptr, d_col, nnz, base));
+    PO_HIP(hipMemcpyAsync(ybuf[0], d_y0, n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    PO_HIP(hipMemsetAsync(upd, 0, n * 2 * sizeof(float), ctx->stream));
+    {   // gains start at 1: fill through the host staging of one float pattern
+        const float one = 1.0f;
+        uint32_t bits;
+        memcpy(&bits, &one, 4);
+        PO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gains), (int)bits, n * 2, ctx->stream));
+    }
+    // scikit-learn's two calls of _gradient_descent: `it` carries over, best_error starts afresh in the second
+    int cur = 0;
+    uint32_t steps = 0, checks = 0;
+    double grad_norm = 0.0;
+    double* scal = nullptr;
+    uint32_t it = 0;
+    tsne_events timing;
+    for (int phase = 0; phase < 2; ++phase) {
+        const uint32_t stop_at = phase == 0 ? (p.exploration_iter < p.max_iter ? p.exploration_iter : p.max_iter) : p.max_iter;
+        const double exaggeration = phase == 0 ? p.early_exaggeration : 1.0, momentum = phase == 0 ? 0.5 : 0.8;
+        const uint32_t patience = phase == 0 ? p.exploration_iter : p.n_iter_without_progress;
+        double best = DBL_MAX;
+        uint32_t best_iter = it;
+        for (; it < stop_at; ++it) {
+            const bool check = (it + 1) % p.n_iter_check == 0;
+            hipEvent_t* ev = nullptr;
+            if (p.time_kernels) {
+                PO_TRY(timing.add4());
+                ev = &timing.ev[timing.ev.size() - 4];
+            }
+            PO_TRY(po_launch_tsne_gradient(ctx, d_rowptr, d_col, d_p, ybuf[cur], n, exaggeration, base, true, nullptr, ybuf[cur ^ 1], upd, gains,
+                                           momentum, p.learning_rate, 0.01, check, check, &scal, ev));
+            cur ^= 1;
+            ++steps;
+            if (!check) continue;
+            PO_HIP(hipMemcpyAsync(ctx->h_tsne, scal, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            PO_HIP(hipStreamSynchronize(ctx->stream));
+            const double err = ctx->h_tsne[1];
+            grad_norm = sqrt(ctx->h_tsne[2]);
+            if (p.history && checks < p.history_cap) {
+                p.history[3 * checks] = (double)(it + 1);
+                p.history[3 * checks + 1] = err;
+                p.history[3 * checks + 2] = grad_norm;
+            }
+            ++checks;
+            PO_REQUIRE(err == err && grad_norm == grad_norm, "%s: the embedding is not finite at iteration %u (NaN in y0 or P?)", who, it + 1);
+            if (err < best) {
+                best = err;
+                best_iter = it;
+            } else if (it - best_iter > patience) {
+                ++it;
+                break;
+            }
+            if (grad_norm <= p.min_grad_norm) {
+                ++it;
+                break;
+            }
+        }
+    }
+    // KL, Z of the embedding that is returned (scikit-learn reports the error of the step before the last update)
+    PO_TRY(po_launch_tsne_gradient(ctx, d_rowptr, d_col, d_p, ybuf[cur], n, 1.0, base, false, upd, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, true,
+                                   false, &scal, nullptr));
+    PO_HIP(hipMemcpyAsync(d_y, ybuf[cur], n * 2 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    PO_HIP(hipMemcpyAsync(ctx->h_tsne, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PO_HIP(hipStreamSynchronize(ctx->stream));
+    if (result) {
+        result->z = ctx->h_tsne[0];
+        result->kl = ctx->h_tsne[1];
+        result->grad_norm = grad_norm;
+        result->iterations = steps;
+        result->history_len = checks;
+        if (steps >= 2 && timing.ev.size() == 4 * (size_t)steps) PO_TRY(timing.medians(steps, result));
+    }
+    return PO_OK;
+}
+
+extern "C" int po_tsne_dev(po_ctx* ctx, uint64_t n, const int64_t* d_rowptr, const int32_t* d_col, const float* d_p, uint64_t nnz,
+                           const float* d_y0, const po_tsne_params* params, float* d_y, po_tsne_result* result) {
+    return tsne_run(ctx, "po_tsne_dev", n, d_rowptr, d_col, d_p, nnz, d_y0, params, d_y, result, false);
+}
+
+// The host-pointer form: the lists, the CSR and the embeddings in ws_tsne_csr, then po_tsne_affinities_dev and tsne_run.  The list
+// rules are asked here first, under this entry point's name, because the staging is sized by them.
+extern "C" int po_tsne(po_ctx* ctx, uint64_t n, uint32_t k, int metric, int val_dtype, const int32_t* idx, const void* val,
+                       double perplexity, const float* y0, const po_tsne_params* params, float* y, po_tsne_result* result) {
+    const char* who = "po_tsne";
+    PO_TRY(po_check_ctx(who, ctx));
+    if (result) memset(result, 0, sizeof(*result));
+    PO_TRY(check_tsne_lists(who, n, k, metric, val_dtype, perplexity));
+    PO_REQUIRE(idx != nullptr && val != nullptr && y0 != nullptr && y != nullptr, "%s: NULL buffer", who);
+    PO_HIP(hipSetDevice(ctx->device));
+    const size_t esz = val_dtype == PO_F32 ? 4 : 8;
+    const uint64_t e = n * (uint64_t)k, cap = 2 * e;
+    int32_t *d_idx = nullptr, *d_col = nullptr;
+    uint8_t* d_val = nullptr;
+    int64_t* d_rowptr = nullptr;
+    float *d_p = nullptr, *d_y0 = nullptr, *d_y = nullptr;
+    PO_TRY(po_stage(ctx, &ctx->ws_tsne_csr, [&](po_carver& ws) {
+        d_idx = ws.array<int32_t>(e);
+        d_val = ws.take(e * esz);
+        d_rowptr = ws.array<int64_t>(n + 1);
+        d_col = ws.array<int32_t>(cap);
+        d_p = ws.array<float>(cap);
+        d_y0 = ws.array<float>(n * 2);
+        d_y = ws.array<float>(n * 2);
+    }));
+    PO_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    PO_HIP(hipMemcpyAsync(d_idx, idx, e * 4, hipMemcpyHostToDevice, ctx->stream));
+    PO_HIP(hipMemcpyAsync(d_val, val, e * esz, hipMemcpyHostToDevice, ctx->stream));
+    PO_HIP(hipMemcpyAsync(d_y0, y0, n * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    uint64_t nnz = 0;
+    PO_TRY(po_tsne_affinities_dev(ctx, n, k, metric, val_dtype, d_idx, d_val, perplexity, nullptr, nullptr, d_rowptr, d_col, d_p, cap, &nnz));
+    PO_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+    PO_TRY(tsne_run(ctx, who, n, d_rowptr, d_col, d_p, nnz, d_y0, params, d_y, result, true));
+    PO_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    PO_HIP(hipMemcpyAsync(y, d_y, n * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    PO_HIP(hipStreamSynchronize(ctx->stream));
+    if (result) {
+        float ms = 0.0f;
+        PO_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        result->affinities_ms = ms;
+        PO_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+        result->optimise_ms = ms;
+    }
     return PO_OK;
 }
