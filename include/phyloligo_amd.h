@@ -399,6 +399,45 @@ int po_silhouette_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, 
 int po_silhouette(po_ctx* ctx, const void* matrix, int dtype, uint64_t n, uint64_t ld, const int32_t* labels, uint32_t n_clusters,
                   double* values, po_silhouette_result* result);
 
+/* ---- DBSCAN on the distance matrix: clusters by density, and a label for the records that belong to none ----------------------- *
+ * The labels_ and core_sample_indices_ of sklearn.cluster.DBSCAN(eps, min_samples, metric="precomputed").fit(matrix), numbering and
+ * border ties included, stated without a visiting order.  The label -1, "no cluster", is what the reference's recommended run
+ * (phyloselect.py -m hdbscan) sends to data_fasta_unclust.fa (bin/phyloselect.py:565-570) and k-medoids cannot give.
+ * matrix: as for k-medoids ([n][n] float32 / float64, ld >= n elements, read by rows, never written); expected to be symmetric,
+ * which is not checked - the result for an asymmetric matrix is unspecified.  Every entry counts as its float64 value.
+ *   neighbours   j is a neighbour of i iff matrix[i][j] <= eps.  The diagonal is taken as stored: a record counts itself through its
+ *                0.  A NaN is never <= eps: a record with an undefined distance is nobody's neighbour (scikit-learn raises).
+ *   degree[i]    the number of neighbours of row i (po_eps_degrees_dev gives just these)
+ *   core[i]      degree[i] >= min_samples
+ *   components   two core records are in one component iff a chain of core records joins them, each link <= eps; a component's
+ *                root is its smallest core index
+ *   ids          0, 1, ... in ascending order of the root (scikit-learn opens clusters in index order of their first core record)
+ *   labels       a core record: its component's id.  Any other record with a core neighbour (a border record): the smallest id
+ *                among its core neighbours' clusters (the first cluster opened that reaches it).  Any other record: -1, noise.
+ * Integer counts and integer minima only: no order of execution changes a result, and the same input gives the same bytes.
+ * The components come from rounds of: the smallest label within eps of every core row (one read of those rows), hooking of each
+ * tree's root onto the smallest label its members saw, pointer jumping; the host reads one flag word per round and the loop ends
+ * with the round that changes nothing (a chain of 4 096 records takes about ten).  Workspace: 5 n integers held by the context.
+ * PO_EINVAL: eps negative or NaN (+inf is allowed: every entry that is not NaN is then a neighbour), min_samples < 1, ld < n,
+ * n > 2^31 - 1, a dtype other than PO_F32 / PO_F64.  n == 0: nothing is done.  po_eps_degrees_dev works on the context's stream
+ * without synchronising it.
+ *   d_degree int32 [n]    d_labels int32 [n]    d_core uint8 [n], 1 = core (may be NULL)
+ *   result (may be NULL; asking for it adds device events and one more synchronisation)                                           */
+typedef struct po_dbscan_result {
+    uint32_t clusters, core, border, noise;   /* core + border + noise = n */
+    uint32_t passes;           /* propagation rounds, the one that changed nothing included (not the degree pass, not the border pass) */
+    uint32_t reserved;
+    double degree_ms;          /* HIP-event times: the degree pass and the split into core and other rows ... */
+    double label_ms;           /* ... the rounds, plus the pass over the rows that are not core ... */
+    double finish_ms;          /* ... the ids, the labels and the counts */
+} po_dbscan_result;
+int po_eps_degrees_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, double eps, int32_t* d_degree);
+int po_dbscan_dev(po_ctx* ctx, const void* d_matrix, int dtype, uint64_t n, uint64_t ld, double eps, int64_t min_samples,
+                  int32_t* d_labels, uint8_t* d_core, po_dbscan_result* result);
+/* Host pointers: the matrix is copied to the device (PO_ENOMEM, with the size in the message, when it does not fit). */
+int po_dbscan(po_ctx* ctx, const void* matrix, int dtype, uint64_t n, uint64_t ld, double eps, int64_t min_samples, int32_t* labels,
+              uint8_t* core, po_dbscan_result* result);
+
 /* ---- row medians of a matrix in HBM ---------------------------------------------------------- *
  * d_out[i] = median of row i of d_matrix [rows][n] (float32 / float64, row major, leading dimension ld >= n elements; read,
  * never written), over all n columns - the diagonal of a distance matrix included: R's apply(dist_matrix, 1, median), the first

@@ -74,6 +74,12 @@ class PoSilhouetteResult(ctypes.Structure):
                 ("sums_ms", ctypes.c_double), ("finish_ms", ctypes.c_double)]
 
 
+class PoDbscanResult(ctypes.Structure):
+    _fields_ = [("clusters", ctypes.c_uint32), ("core", ctypes.c_uint32), ("border", ctypes.c_uint32), ("noise", ctypes.c_uint32),
+                ("passes", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("degree_ms", ctypes.c_double),
+                ("label_ms", ctypes.c_double), ("finish_ms", ctypes.c_double)]
+
+
 PO_SILHOUETTE_CHUNK = 16     # clusters per matrix read of the silhouette entry points (include/phyloligo_amd.h)
 
 
@@ -132,6 +138,9 @@ SIGNATURES = {
     "po_cluster_sums_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _u32, _vp]),
     "po_silhouette_dev": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _u32, _vp, _c.POINTER(PoSilhouetteResult)]),
     "po_silhouette": (_int, [_vp, _vp, _int, _u64, _u64, _vp, _u32, _vp, _c.POINTER(PoSilhouetteResult)]),
+    "po_eps_degrees_dev": (_int, [_vp, _vp, _int, _u64, _u64, _dbl, _vp]),
+    "po_dbscan_dev": (_int, [_vp, _vp, _int, _u64, _u64, _dbl, _c.c_int64, _vp, _vp, _c.POINTER(PoDbscanResult)]),
+    "po_dbscan": (_int, [_vp, _vp, _int, _u64, _u64, _dbl, _c.c_int64, _vp, _vp, _c.POINTER(PoDbscanResult)]),
     "po_row_medians_dev": (_int, [_vp, _vp, _int, _u64, _u64, _u64, _vp]),
     "po_row_medians_passes": (_int, [_vp, _c.POINTER(_u64)]),
     "po_fasta_scan": (_int, [_vp, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoKmedoidsResult, PoSilhouetteResult, PoStats, PoTsneParams, PoTsneResult,
+from ._lib import (METRICS, STRANDS, PO_F32, PO_F64, PO_FLAG_NO_SYMMETRY, PO_FLAG_NO_TABLE_PATH, PO_FLAG_NO_RC_FOLD, PO_FLAG_PAIRDOT_I8, PO_FLAG_NO_PAIRDOT, PO_KNN_MAX_K, PoBlock, PoDbscanResult, PoKmedoidsResult, PoSilhouetteResult, PoStats, PoTsneParams, PoTsneResult,
                    check)
 
 
@@ -625,6 +625,49 @@ class Context:
             return values, {"mean": res.mean, "nonempty_clusters": res.nonempty_clusters, "passes": res.passes,
                             "sums_ms": res.sums_ms, "finish_ms": res.finish_ms}
         return values
+
+    # ---- DBSCAN on a distance matrix ---------------------------------------------------------------
+    def eps_degrees(self, matrix, eps):
+        """int32 [n]: for every row of a distance matrix [n, n] the number of entries <= eps, the diagonal as stored, a NaN never
+        (po_eps_degrees_dev): the neighbourhood sizes DBSCAN compares with min_samples.  numpy in -> numpy out (the matrix is
+        copied to the device); torch CUDA tensor in -> tensor out on torch's current stream."""
+        import torch
+        is_t, matrix, code, n, ld = self._matrix_on_device(matrix)
+        out = torch.empty((n,), dtype=torch.int32, device=matrix.device)
+        self._use_torch_stream()
+        check(self._lib.po_eps_degrees_dev(self._h, matrix.data_ptr(), code, n, ld, float(eps), out.data_ptr()))
+        return out if is_t else out.cpu().numpy()
+
+    def dbscan(self, matrix, eps, min_samples=5, want_stats=False):
+        """DBSCAN of a precomputed distance matrix [n, n] (float32 / float64, unit inner stride, any row stride >= n; symmetric):
+        the labels_ and core samples of sklearn.cluster.DBSCAN(eps=eps, min_samples=min_samples, metric="precomputed").fit(matrix),
+        numbering and border ties included (include/phyloligo_amd.h has the six rules).  An entry <= eps makes two records
+        neighbours, compared as float64; a NaN never does, where scikit-learn raises.  Returns (labels int32 [n], -1 = noise;
+        core mask bool [n]); with want_stats also a dict (clusters, core, border, noise, passes = propagation rounds, degree_ms /
+        label_ms / finish_ms).  numpy in -> numpy out (po_dbscan: the matrix is copied to the device); torch CUDA tensor in ->
+        tensors out on torch's current stream (po_dbscan_dev)."""
+        is_t, matrix, code, n, ld = self._matrix_arg(matrix)
+        if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)):
+            raise _lib.PhyloligoError(_lib.PO_EINVAL, "min_samples must be an integer (got %r)" % (min_samples,))
+        res = PoDbscanResult()
+        rp = ctypes.byref(res) if want_stats else None
+        if is_t:
+            import torch
+            labels = torch.empty((n,), dtype=torch.int32, device=matrix.device)
+            core = torch.empty((n,), dtype=torch.uint8, device=matrix.device)
+            self._use_torch_stream()
+            check(self._lib.po_dbscan_dev(self._h, matrix.data_ptr(), code, n, ld, float(eps), int(min_samples), labels.data_ptr(),
+                                          core.data_ptr(), rp))
+            core = core.view(torch.bool)
+        else:
+            labels = np.zeros(n, dtype=np.int32)
+            core = np.zeros(n, dtype=np.uint8)
+            check(self._lib.po_dbscan(self._h, _np_ptr(matrix), code, n, ld, float(eps), int(min_samples), _np_ptr(labels), _np_ptr(core), rp))
+            core = core.view(np.bool_)
+        if want_stats:
+            return labels, core, {"clusters": res.clusters, "core": res.core, "border": res.border, "noise": res.noise,
+                                  "passes": res.passes, "degree_ms": res.degree_ms, "label_ms": res.label_ms, "finish_ms": res.finish_ms}
+        return labels, core
 
     # ---- row medians of a matrix (the reference's outlier clip) -----------------------------------
     def row_medians(self, matrix):

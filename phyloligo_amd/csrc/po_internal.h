@@ -93,6 +93,8 @@ struct po_ctx {
     po_buf ws_rowmed;                  // row medians: the counter of row reads of the last call (po_rowmedian.hip)
     po_buf ws_sil;                     // silhouettes: labels, cluster sizes, one pass's sums [n][PO_SILHOUETTE_CHUNK], two doubles per row (po_silhouette.hip)
     double* h_sil = nullptr;           // pinned: 8 doubles read back by the silhouette entry points
+    po_buf ws_dbscan;                  // DBSCAN: degrees, the two row lists, two label arrays, row minima, counts (po_dbscan.hip)
+    uint32_t* h_dbscan = nullptr;      // pinned: 8 words read back by po_dbscan_dev
     void* h_stage[2] = {nullptr, nullptr};   // pinned staging buffers of po_pairwise / po_pairwise_freq (copy_rows_to_host, po_pairwise.hip)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };

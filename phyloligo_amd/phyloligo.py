@@ -387,6 +387,20 @@ def get_cmd(argv=None):
                         help="with --kmedoids or --kmedoids-sweep: write the silhouette value of every contig for the labels written to "
                              "-o to FILE, one per line in input order (sklearn.metrics.silhouette_samples on the matrix in GPU memory; "
                              "a value near 0 or below marks a contig between two clusters)")
+    parser.add_argument("--dbscan", action="store", dest="dbscan", type=float, default=None, metavar="EPS",
+                        help="not in the reference's phyloligo.py: cluster the contigs by density with DBSCAN on the N x N matrix, "
+                             "which stays in GPU memory, and write one cluster label per contig to -o, in input order; two contigs "
+                             "are neighbours when their distance is at most EPS, and a contig that belongs to no cluster gets -1 "
+                             "(what phyloselect.py -m hdbscan sends to data_fasta_unclust.fa); the labels are those of "
+                             "sklearn.cluster.DBSCAN(eps=EPS, metric=\"precomputed\"); EPS >= 0")
+    parser.add_argument("--dbscan-min-samples", action="store", dest="dbscan_min_samples", type=int, default=5, metavar="M",
+                        help="with --dbscan: a contig with at least M contigs within EPS, itself included, is a core contig, "
+                             "scikit-learn's min_samples [default:%(default)d]")
+    parser.add_argument("--dbscan-dtype", action="store", dest="dbscan_dtype", choices=["float64", "float32"], default="float64",
+                        help="with --dbscan: element type of the matrix in GPU memory; float32 takes half the memory "
+                             "[default:%(default)s]")
+    parser.add_argument("--dbscan-core", action="store", dest="dbscan_core", default=None, metavar="FILE",
+                        help="with --dbscan: write one line per contig to FILE, 1 for a core contig and 0 for any other")
     parser.add_argument("--clip-percentile", action="store", dest="clip_percentile", type=float, default=1.0, metavar="P",
                         help="not in the reference's phyloligo.py: before anything is computed from the matrix, drop the contigs whose "
                              "median distance to all contigs lies above the P quantile of those medians (what phyloselect.R -c P "
@@ -527,9 +541,33 @@ def _kmedoids_refused(params, environ=os.environ):
                          values=values(), ranks="clustering")
 
 
+def _dbscan_refused(params, environ=os.environ):
+    """the reason --dbscan (and --dbscan-core with it) cannot run with these options, or None"""
+    eps = getattr(params, "dbscan", None)
+    if eps is None:
+        if getattr(params, "dbscan_core", None) is not None:
+            return "Error, --dbscan-core marks the core contigs of a density clustering: give --dbscan EPS with it"
+        return None
+
+    def first():
+        if (params.kmedoids is not None or getattr(params, "kmedoids_sweep", None) is not None or params.knn is not None or
+                getattr(params, "tsne", None) is not None):
+            yield ("Error, --dbscan, --kmedoids and --kmedoids-sweep write cluster labels to -o, --knn a neighbour graph and --tsne an "
+                   "embedding: give one of them")
+
+    def values():
+        if not eps >= 0.0:
+            yield "Error, --dbscan EPS needs a distance EPS >= 0 (got %g)" % eps
+        if params.dbscan_min_samples < 1:
+            yield "Error, --dbscan-min-samples M needs M >= 1 contigs (got %d)" % params.dbscan_min_samples
+
+    return _first_reason(params, environ, "--dbscan", first(), writes="one label per contig as text", kt="larger means closer",
+                         values=values(), ranks="clustering")
+
+
 def refusal(params, environ=os.environ):
     """the first reason this command line cannot run, or None; a new mode adds its function here, where main() is to ask it"""
-    for refused in (_clip_refused, _kmedoids_refused, _tsne_refused, _knn_refused):
+    for refused in (_clip_refused, _kmedoids_refused, _dbscan_refused, _tsne_refused, _knn_refused):
         reason = refused(params, environ)
         if reason:
             return reason
@@ -547,10 +585,10 @@ def refuse(reason, speak=True):
 def launch_plan(params, environ):
     """What `python -m phyloligo_amd` decides before anything touches torch or the library: (the reason to refuse or None,
     the GPUs asked for, whether torch has to be loaded before the library).  torch comes first exactly where the run keeps the
-    matrix in a torch tensor (k-medoids, the sweep, an active clip) or is one of several ranks: it bundles its own HIP runtime, and
-    a process must hold exactly one (_lib.PREFER_NO_TORCH)."""
+    matrix in a torch tensor (k-medoids, the sweep, DBSCAN, an active clip) or is one of several ranks: it bundles its own HIP
+    runtime, and a process must hold exactly one (_lib.PREFER_NO_TORCH)."""
     needs_torch = (int(environ.get("WORLD_SIZE", "1")) > 1 or params.kmedoids is not None or params.kmedoids_sweep is not None or
-                   _clip_active(params))
+                   getattr(params, "dbscan", None) is not None or _clip_active(params))
     return refusal(params, environ), params.gpus, needs_torch
 
 
@@ -630,7 +668,8 @@ def _clip(params, frequencies):
     print("Clipping outlier contigs")
     n = frequencies.shape[0]
     ctx = _context()
-    f32 = params.large in ("memmap", "h5py") or params.kmedoids_dtype == "float32"      # the run's output is float32 data anyway
+    f32 = (params.large in ("memmap", "h5py") or params.kmedoids_dtype == "float32" or      # the run's output is float32 data anyway
+           getattr(params, "dbscan_dtype", "float64") == "float32")
     t0 = time.perf_counter()
     medians = np.zeros(0)
     t1 = t2 = t0
@@ -778,6 +817,44 @@ def _kmedoids_mode(params, frequencies):
     return "matrix + k-medoids", "Writing cluster labels", write, dict(st, rows=[0, n]), stats
 
 
+def write_core(path, core):
+    """one line per contig, in input order: 1 for a core contig, 0 for any other"""
+    with open(path, "w") as fh:
+        fh.write("".join("1\n" if x else "0\n" for x in core))
+
+
+def _dbscan_mode(params, frequencies):
+    """--dbscan: the dense matrix computed into device memory (po_pairwise_dev), its neighbourhoods counted and its core contigs
+    joined there (po_eps_degrees_dev, po_dbscan_dev); only the labels, the core mask and the degrees come back"""
+    n = frequencies.shape[0]
+    ctx = _context()
+    eps, m = params.dbscan, params.dbscan_min_samples
+    if n < 1:
+        refuse("Error, --dbscan needs at least 1 contig (got %d)" % n)
+    buf, _, st = _device_matrix(params, ctx, frequencies, params.dbscan_dtype == "float32", "--dbscan", "--dbscan-dtype float32")
+    t0 = time.perf_counter()
+    try:
+        d_labels, d_core, ds = ctx.dbscan(buf[:, :n], eps, m, want_stats=True)
+        degree = ctx.eps_degrees(buf[:, :n], eps).cpu().numpy() if params.json_stats else None
+    except api._lib.PhyloligoError as e:
+        refuse("Error, --dbscan: %s" % e)
+    labels, core = d_labels.cpu().numpy(), d_core.cpu().numpy()
+    stats = {"dbscan_eps": eps, "dbscan_min_samples": m, "dbscan_dtype": params.dbscan_dtype, "dbscan_clusters": ds["clusters"],
+             "dbscan_core": ds["core"], "dbscan_border": ds["border"], "dbscan_noise": ds["noise"], "dbscan_passes": ds["passes"],
+             "dbscan_sizes": [int(x) for x in np.bincount(labels[labels >= 0], minlength=ds["clusters"])],
+             "dbscan_ms": (time.perf_counter() - t0) * 1e3,
+             "dbscan_phases_ms": {p: ds[p + "_ms"] for p in ("degree", "label", "finish")}}
+    if degree is not None:
+        stats.update(dbscan_degree_min=int(degree.min()), dbscan_degree_median=float(np.median(degree)), dbscan_degree_max=int(degree.max()))
+
+    def write():
+        write_labels(params.out_file, labels)
+        if params.dbscan_core is not None:
+            write_core(params.dbscan_core, core)
+
+    return "matrix + DBSCAN", "Writing cluster labels", write, dict(st, rows=[0, n]), stats
+
+
 def main(argv=None, params=None):
     """phyloligo.py:1036-1068 around whichever mode the options choose.  params: the command line as `python -m phyloligo_amd`
     has parsed it already."""
@@ -810,6 +887,7 @@ def main(argv=None, params=None):
     if frequencies is None:                              # an unknown --method: compute_frequencies has said so (:995 only prints)
         return 0
     mode = (_kmedoids_mode if params.kmedoids is not None or params.kmedoids_sweep is not None else
+            _dbscan_mode if getattr(params, "dbscan", None) is not None else
             _tsne_mode if params.tsne is not None else _knn_mode if params.knn is not None else _matrix_mode)
     label, announce, write, stage2, stats = mode(params, frequencies)
     t_dist = time.perf_counter()
