@@ -128,6 +128,51 @@ template <> struct rows_vec<16> {
     static __device__ __forceinline__ type load(const uint32_t* p) { type v; asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(v) : "s"(p)); return v; }
 };
 
+// ---- the mirrored tile of a float64 matrix, transposed in registers ---------------------------------------------------------
+// A wave holds 16 rows x 128 columns, a lane two columns of them: for each of its columns a lane already has the whole 128-byte
+// line (16 float64) that the wave contributes to that row of the mirror.  What a store instruction wants is 8 consecutive lanes
+// x 16 bytes on ONE line, i.e. an 8 x 8 transpose of 16-byte elements (row pairs) inside every group of 8 lanes.  Three exchange
+// stages do it with DPP moves: in stage M (1, 2, 4) lane i and lane i ^ M swap the elements whose slot index differs from the
+// lane index in bit M.  Lane and slot bits trade places one by one: afterwards x[s] of lane 8 g + i is row pair i of the column
+// that lane 8 g + s held.  No LDS memory, no barrier: the lookups' pipe is left alone and the table survives the epilogue.
+template <int CTRL> __device__ __forceinline__ double po_dpp_mov_f64(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+// the lanes of the banks (groups of four lanes) in BANK take `src` through CTRL, the others keep `old`
+template <int CTRL, int BANK> __device__ __forceinline__ double po_dpp_banks_f64(double old, double src) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xF, BANK, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xF, BANK, false);
+    return __hiloint2double(hi, lo);
+}
+// M = 1, 2: the partner sits in the same quad (quad_perm CTRL = lane ^ M); which slot a lane sends depends on its own bit M
+template <int M, int CTRL> __device__ __forceinline__ void po_tr8_quad_stage(double (&x)[8][2], bool set) {
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        if (p & M) continue;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const double got = po_dpp_mov_f64<CTRL>(set ? x[p][h] : x[p | M][h]);
+            x[p][h] = set ? got : x[p][h];
+            x[p | M][h] = set ? x[p | M][h] : got;
+        }
+    }
+}
+__device__ __forceinline__ void po_transpose8(double (&x)[8][2], uint32_t lane) {
+    po_tr8_quad_stage<1, 0xB1>(x, (lane & 1u) != 0);                             // quad_perm:[1,0,3,2]
+    po_tr8_quad_stage<2, 0x4E>(x, (lane & 2u) != 0);                             // quad_perm:[2,3,0,1]
+    // M = 4: the partner is four lanes up (banks 0 and 2 of a row of 16) or down (banks 1 and 3): the bank mask is the select
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const double lo = x[p][h], hi = x[p | 4][h];
+            x[p | 4][h] = po_dpp_banks_f64<0x104, 0x5>(hi, lo);                  // row_shl:4: lane i reads lane i + 4
+            x[p][h] = po_dpp_banks_f64<0x114, 0xA>(lo, hi);                      // row_shr:4: lane i reads lane i - 4
+        }
+}
+
 // RW = 16 rows per wave: 8 waves per tile (512 lanes), 4 waves per SIMD at two workgroups per CU.  (8 rows per wave, 16 waves per
 // tile and 8 per SIMD measured 15.3 - 15.7 ms: more waves do not buy more overlap.)
 template <typename OUT, int RW>
@@ -321,6 +366,24 @@ __global__ __launch_bounds__(64 * TM / RW, 4) void jsd_lut_rows_kernel(po_tile_a
             }
         }
         if (!mirrors) return;
+        if constexpr (RW == 16 && std::is_same<OUT, double>::value) {
+            // the transposed tile straight from registers (po_transpose8): per column parity e, lane 8 g + i ends up with row pair
+            // i of columns 16 g + 2 s + e, s = 0 .. 7, and store s of the wave writes eight whole 128-byte lines of the mirror.
+            // (A float32 line of a wave's 16 rows is 64 bytes, half a line per 8 lanes: that type keeps the LDS path below.)
+            const uint64_t mpitch = A.ld_mirror * sizeof(OUT);
+            char* mlane = reinterpret_cast<char*>(mir + (j0 - A.col_begin + 16 * (lane >> 3)) * A.ld_mirror +
+                                                  (ib - A.row_begin) + 2 * (lane & 7u));
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                double x[8][2];
+#pragma unroll
+                for (int p = 0; p < 8; ++p) { x[p][0] = acc[2 * p][e]; x[p][1] = acc[2 * p + 1][e]; }
+                po_transpose8(x, lane);
+#pragma unroll
+                for (int s = 0; s < 8; ++s) po_store2(reinterpret_cast<OUT*>(mlane + (2 * s + e) * mpitch), x[s][0], x[s][1]);
+            }
+            return;
+        }
         // the transposed tile, 64 columns at a time through LDS (the table is dead): full 1 KiB row pieces again
         const uint32_t loff = 2 * lane * (uint32_t)sizeof(OUT);
         const uint64_t mpitch = A.ld_mirror * sizeof(OUT);
