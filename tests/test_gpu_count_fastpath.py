@@ -137,7 +137,7 @@ def test_long_records_go_through_segment_rows(ctx, pattern, strand, seed):
     second call on the same context (the scratch rows have to be zero again) with the records in reverse order."""
     import torch
     rng = np.random.default_rng(900 + seed)
-    span = 2016                                                       # window starts per chunk (kChunkSpan)
+    span = 2016                                                       # window starts per chunk (kSpan)
     lens = []
     for _ in range(int(rng.integers(5, 60))):
         lens.append(int(rng.integers(1, 5000)))
@@ -171,3 +171,36 @@ def test_long_records_go_through_segment_rows(ctx, pattern, strand, seed):
     assert np.array_equal(t, ot) and np.array_equal(c, oc)
     c, t = run(order[::-1])
     assert np.array_equal(t, ot[::-1]) and np.array_equal(c, oc[::-1])
+
+
+@pytest.mark.parametrize("n", [1_048_576, 1_048_577])
+def test_both_sides_of_the_scan_switch(ctx, n):
+    """The chunk scan is one launch up to 1 024 workgroups of 1 024 records (kOnePassBlocks) and three launches beyond; the two
+    build the same tables: chunk_start by a 256-lane scan per workgroup, and the chunk -> record map.  One record
+    more than the switch and one less: records of 0 - 40 bases (1 in 500 bytes an N) and three that span chunks - about 5 chunks
+    (written by their own lane of the scan) in front, about 300 (more than kWaveFillChunks: the scan leaves their entries
+    unwritten and count_kernel searches) as the last record of the scan's first workgroup, about 40 (written by the whole wave)
+    as the last record.  Against the oracle on the first and the last 2 000 records, 3 000 sampled ones and the three long ones;
+    every row's sum equals its total; a second call on the same context gives the same tensors."""
+    import torch
+    rng = np.random.default_rng(n)
+    lens = rng.integers(0, 41, size=n).astype(np.int64)
+    long_ones = {0: 5 * 2016 - 77, 1023: 300 * 2016 + 5, n - 1: 40 * 2016 - 1000}
+    for i, length in long_ones.items():
+        lens[i] = length
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    seq = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=int(off[-1]))]
+    seq[rng.random(seq.size) < 0.002] = ord("N")
+    picked = np.unique(np.concatenate([np.arange(2000), np.arange(n - 2000, n), rng.integers(0, n, size=3000), np.array(list(long_ones))]))
+    oc, ot = oracle.compute_counts([seq[off[i]:off[i + 1]].tobytes() for i in picked], "11", "both")
+
+    d_seq, d_off = torch.from_numpy(seq).cuda(), torch.from_numpy(off).cuda()
+    counts, totals = ctx.count_profiles(d_seq, d_off, "11", "both")
+    assert torch.equal(counts.sum(dim=1, dtype=torch.int64), totals)
+    where = torch.from_numpy(picked).cuda()
+    assert np.array_equal(totals[where].cpu().numpy(), np.asarray(ot).astype(np.int64))
+    bad = np.nonzero((counts[where].cpu().numpy().astype(np.int64) != oc).any(axis=1))[0]
+    assert bad.size == 0, ("records", picked[bad[:8]], lens[picked[bad[:8]]])
+    again, totals_again = ctx.count_profiles(d_seq, d_off, "11", "both")
+    assert torch.equal(again, counts) and torch.equal(totals_again, totals)
