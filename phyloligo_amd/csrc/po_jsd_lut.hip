@@ -17,6 +17,7 @@
 
 #include <stdlib.h>
 
+#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -110,7 +111,7 @@ __global__ void lut_table_kernel(double* __restrict__ lut, const uint32_t* __res
 // same for every lane: they are fetched by ONE scalar load (s_load_dwordx8 / x16 from the transposed count matrix) and sit in
 // scalar registers, so that a lookup address is one v_add_u32 in its short encoding (scalar row term + vector column term) and
 // nothing else; the two column counts of a word come straight from global memory (8 bytes per lane, 512 contiguous bytes per
-// wave, requested kPF words ahead) with the lane's table copy baked in (ctb).  No operand goes through LDS any more - no
+// wave, kept in a ring of kPF words) with the lane's table copy baked in (ctb).  No operand goes through LDS any more - no
 // LDS-DMA staging, no barrier in the loop - and the LDS data path serves nothing but the lookups (the round-1/2 kernel, a
 // 4 x 8 register block per lane with both operands staged through LDS, spent 1 ds_read_b128 + 4 ds_read_b64 of every 84 LDS
 // cycles and 10 of every 42 vector adds on operands; it measured 15.1 - 15.4 ms at C2 against 15.0 - 15.2 ms for this one on
@@ -118,9 +119,15 @@ __global__ void lut_table_kernel(double* __restrict__ lut, const uint32_t* __res
 // word's row counts are requested before the current word's lookups and waited for behind them with lgkmcnt(0) (the
 // compiler does not know about them; its own counted waits only ever wait longer because of them).
 typedef uint32_t po_u32x16 __attribute__((ext_vector_type(16)));
+// a word's two column terms, read through a pointer that says "global memory" (a native vector, not uint2: copying a struct goes
+// through a generic reference, and the load would be a flat one, counted by lgkmcnt like the lookups)
+typedef uint32_t po_u32x2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(1))) po_u32x2* po_global_u2;
 constexpr int kRowsMirrorCols = 64;                     // columns per transposition round of the mirrored tile
 constexpr int kRowsMirrorBytes = kRowsMirrorCols * kMirrorLdsStride * 8;
 constexpr int kRowsLdsBytes = kRowsMirrorBytes > kLutBytes ? kRowsMirrorBytes : kLutBytes;
+// widest mirror row (bytes) at which a lane's offset from its wave's first mirror row, at most 112 rows + 112 bytes, is 32 bits
+constexpr uint64_t kMirrorPitchMax = (0xFFFFFFFFull - 112) / 112;
 
 template <int RW> struct rows_vec;
 template <> struct rows_vec<16> {
@@ -204,18 +211,17 @@ __global__ __launch_bounds__(64 * TM / RW, 4) void jsd_lut_rows_kernel(po_tile_a
     const uint32_t* pa = ct + i0 + RW * wv;                                      // + k * npad: wave uniform
     const uint32_t* pb = ctb + j0;                                               // + k * npad, + 2 lane
     const uint32_t lb = 2 * lane;
-    const uint32_t tbase = po_lds_addr(tab);
     // The word loop runs over the zero-padded width D8 (prep_counts_kernel pads Ct / Ctb to whole groups of 8 words; a padded
     // word looks up T[0 + 0] = 0), NOT over A.dim: a round takes four words, and clamping the operand pointers at the last REAL
     // word of a width that is not a multiple of 4 would add that word's lookup again for every surplus slot.
     const uint32_t dim8 = (A.dim + 7u) & ~7u;
     const uint32_t kmax = dim8 - 1;
     // (operand pointers advance by one word row per step, clamped at the last word: scalar adds, no 64-bit multiplies and no
-    // vector address arithmetic in the loop; the table's LDS base goes onto the two column terms, not onto the 16 row terms -
-    // the scalar unit issued half as many instructions as the vector unit before: SQ_INSTS_SALU 3.2e9 against 6.0e9)
-    uint2 bq[kPF];
+    // vector address arithmetic in the loop.  The table starts at LDS address 0 - the kernel has no static LDS, which
+    // po_launch_jsd_lut_tiles checks - so a column term IS the lookup address of row count 0 and goes into the asm as loaded.)
+    po_u32x2 bq[kPF];
 #pragma unroll
-    for (int q = 0; q < kPF; ++q) bq[q] = *reinterpret_cast<const uint2*>(pb + (uint64_t)min((uint32_t)q, kmax) * A.npad + lb);
+    for (int q = 0; q < kPF; ++q) bq[q] = *(po_global_u2)(pb + (uint64_t)min((uint32_t)q, kmax) * A.npad + lb);
     const uint32_t* pb_pf = pb + (uint64_t)min((uint32_t)kPF, kmax) * A.npad;    // the word the next refill of the ring reads
     const uint32_t* pa_nx = pa + (uint64_t)min(2u, kmax) * A.npad;              // the word whose row counts are requested next
     AV a_c0 = rows_vec<RW>::load(pa);                                            // words are taken in pairs: one wait for the scalar
@@ -270,11 +276,6 @@ __global__ __launch_bounds__(64 * TM / RW, 4) void jsd_lut_rows_kernel(po_tile_a
         if (!CLAMP || k + 3 <= kmax) pa_nx += A.npad;
         AV a_n1 = rows_vec<RW>::load(pa_nx);
         if (!CLAMP || k + 4 <= kmax) pa_nx += A.npad;
-        const uint32_t b0 = bq[q].x + tbase, b1 = bq[q].y + tbase, c0 = bq[q + 1].x + tbase, c1 = bq[q + 1].y + tbase;
-        bq[q] = *reinterpret_cast<const uint2*>(pb_pf + lb);
-        if (!CLAMP || k + kPF + 1 <= kmax) pb_pf += A.npad;
-        bq[q + 1] = *reinterpret_cast<const uint2*>(pb_pf + lb);
-        if (!CLAMP || k + kPF + 2 <= kmax) pb_pf += A.npad;
         double n0, n1, n2, n3, m0, m1, m2, m3;
         uint32_t t0, t1, t2, t3;
         double* accf = &acc[0][0];                        // c<2r+e> = acc[r][e]
@@ -290,10 +291,20 @@ __global__ __launch_bounds__(64 * TM / RW, 4) void jsd_lut_rows_kernel(po_tile_a
                        PO_G_ACC(24), PO_G_ACC(25), PO_G_ACC(26), PO_G_ACC(27), PO_G_ACC(28), PO_G_ACC(29), PO_G_ACC(30), PO_G_ACC(31),
                        [n0] "=&v"(n0), [n1] "=&v"(n1), [n2] "=&v"(n2), [n3] "=&v"(n3), [m0] "=&v"(m0), [m1] "=&v"(m1), [m2] "=&v"(m2), [m3] "=&v"(m3),
                        [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), "+s"(a_n0), "+s"(a_n1)
-                     : PO_G_ROWS(a, a_c0), PO_G_ROWS(e, a_c1), [b0] "v"(b0), [b1] "v"(b1), [d0] "v"(c0), [d1] "v"(c1)
+                     : PO_G_ROWS(a, a_c0), PO_G_ROWS(e, a_c1), [b0] "v"(bq[q].x), [b1] "v"(bq[q].y), [d0] "v"(bq[q + 1].x), [d1] "v"(bq[q + 1].y)
                      : "memory");
         a_c0 = a_n0;
         a_c1 = a_n1;
+        // The two ring slots just consumed are refilled BEHIND the asm statement, into the registers it read: no copy of them is
+        // needed.  They are next read one whole asm statement later (vmcnt(2) in front of it: the compiler tracks these loads).
+        // The empty asm keeps the row pointer a scalar pair of its own, so that a load is base (scalar) + 8 lane (one 32-bit
+        // vector offset for the whole loop); left alone the compiler keeps a 64-bit address per lane and slot and steps each of
+        // them with a vector add per word.
+        asm volatile("" : "+s"(pb_pf));
+        bq[q] = *(po_global_u2)(pb_pf + lb);
+        if (!CLAMP || k + kPF + 1 <= kmax) pb_pf += A.npad;
+        bq[q + 1] = *(po_global_u2)(pb_pf + lb);
+        if (!CLAMP || k + kPF + 2 <= kmax) pb_pf += A.npad;
     };
     auto round = [&](uint32_t k0, auto clamp_tag) {
         pair_of_words(k0, 0, clamp_tag);
@@ -353,7 +364,8 @@ __global__ __launch_bounds__(64 * TM / RW, 4) void jsd_lut_rows_kernel(po_tile_a
     const bool interior = i0 >= A.row_begin && i0 + TM <= n_rows && j0 >= A.col_begin && j0 + TN <= n_cols &&
                           ((A.ld_out | (j0 - A.col_begin)) & 1) == 0 && (reinterpret_cast<uintptr_t>(A.out) & (2 * sizeof(OUT) - 1)) == 0 &&
                           (!mirrors || (((A.ld_mirror | (i0 - A.row_begin)) & 1) == 0 &&
-                                        (reinterpret_cast<uintptr_t>(A.mirror) & (2 * sizeof(OUT) - 1)) == 0));
+                                        (reinterpret_cast<uintptr_t>(A.mirror) & (2 * sizeof(OUT) - 1)) == 0 &&
+                                        A.ld_mirror * sizeof(OUT) <= kMirrorPitchMax));   // (112 rows + 112 bytes in 32 bits)
     if (interior) {
         {   // the tile itself: a row of it is 1 KiB (float64) of one wave-instruction
             char* rowp = reinterpret_cast<char*>(out + (ib - A.row_begin) * A.ld_out + (j0 - A.col_begin));   // uniform
@@ -370,17 +382,25 @@ __global__ __launch_bounds__(64 * TM / RW, 4) void jsd_lut_rows_kernel(po_tile_a
             // the transposed tile straight from registers (po_transpose8): per column parity e, lane 8 g + i ends up with row pair
             // i of columns 16 g + 2 s + e, s = 0 .. 7, and store s of the wave writes eight whole 128-byte lines of the mirror.
             // (A float32 line of a wave's 16 rows is 64 bytes, half a line per 8 lanes: that type keeps the LDS path below.)
+            // Addresses like the tile's own: a uniform row base stepped by the pitch on the scalar unit plus one 32-bit lane
+            // offset (16 (lane >> 3) rows down, 2 (lane & 7) values in), which `interior` has checked to fit.
             const uint64_t mpitch = A.ld_mirror * sizeof(OUT);
-            char* mlane = reinterpret_cast<char*>(mir + (j0 - A.col_begin + 16 * (lane >> 3)) * A.ld_mirror +
-                                                  (ib - A.row_begin) + 2 * (lane & 7u));
+            const uint32_t moff = 16 * (lane >> 3) * (uint32_t)mpitch + 2 * (lane & 7u) * (uint32_t)sizeof(OUT);
+            char* mrow0 = reinterpret_cast<char*>(mir + (j0 - A.col_begin) * A.ld_mirror + (ib - A.row_begin));   // uniform
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 double x[8][2];
 #pragma unroll
                 for (int p = 0; p < 8; ++p) { x[p][0] = acc[2 * p][e]; x[p][1] = acc[2 * p + 1][e]; }
                 po_transpose8(x, lane);
+                char* mrow = mrow0 + e * mpitch;
+                uint32_t moff_e = moff;
+                asm volatile("" : "+v"(moff_e));                                 // (one offset register per pass: keeps base + offset apart)
 #pragma unroll
-                for (int s = 0; s < 8; ++s) po_store2(reinterpret_cast<OUT*>(mlane + (2 * s + e) * mpitch), x[s][0], x[s][1]);
+                for (int s = 0; s < 8; ++s) {
+                    po_store2(reinterpret_cast<OUT*>(mrow + moff_e), x[s][0], x[s][1]);
+                    mrow += 2 * mpitch;
+                }
             }
             return;
         }
@@ -492,6 +512,21 @@ int po_launch_jsd_lut_prep(po_ctx* ctx, const uint32_t* d_counts, const uint64_t
     return PO_OK;
 }
 
+// jsd_lut_rows_kernel adds no base to its lookup addresses: the table has to start at LDS address 0, which it does as long as
+// the kernel declares no static LDS in front of its dynamic array.  That is a property of the compiled code, asked of the
+// runtime once per instantiation (known: 0 not yet, 1 yes, -1 no).
+static int table_at_lds_zero(const void* kernel, std::atomic<int>& known) {
+    int k = known.load(std::memory_order_relaxed);
+    if (k == 0) {
+        hipFuncAttributes fa;
+        PO_HIP(hipFuncGetAttributes(&fa, kernel));
+        k = fa.sharedSizeBytes == 0 ? 1 : -1;
+        known.store(k, std::memory_order_relaxed);
+    }
+    if (k < 0) { po_set_error("jsd_lut_rows_kernel was built with static LDS: its table would not start at LDS address 0"); return PO_EUNSUPPORTED; }
+    return PO_OK;
+}
+
 int po_launch_jsd_lut_tiles(po_ctx* ctx, const po_tile_args& a, uint64_t n, const void* ws, uint64_t* tiles) {
     const uint8_t* base = static_cast<const uint8_t*>(ws);
     const uint32_t* ct = reinterpret_cast<const uint32_t*>(base);
@@ -508,6 +543,10 @@ int po_launch_jsd_lut_tiles(po_ctx* ctx, const po_tile_args& a, uint64_t n, cons
     if (nblocks >= (1ull << 31)) { po_set_error("too many tiles for one launch (%llu)", (unsigned long long)nblocks); return PO_EUNSUPPORTED; }
     constexpr int RWL = 16;
     const size_t shmem = kRowsLdsBytes;
+    static std::atomic<int> lds_zero_f32{0}, lds_zero_f64{0};
+    if (int rc = a.out_f32 ? table_at_lds_zero(reinterpret_cast<const void*>(jsd_lut_rows_kernel<float, RWL>), lds_zero_f32)
+                           : table_at_lds_zero(reinterpret_cast<const void*>(jsd_lut_rows_kernel<double, RWL>), lds_zero_f64))
+        return rc;
     if (a.out_f32) {
         PO_SHMEM(ctx, (jsd_lut_rows_kernel<float, RWL>), shmem);
         hipLaunchKernelGGL((jsd_lut_rows_kernel<float, RWL>), dim3((uint32_t)nblocks), dim3(64 * TM / RWL), shmem, ctx->stream, a, ct, ctb, lut, cls, clsk);
